@@ -2,8 +2,14 @@
 taxonomy, one data-parallel training step per "step", 256 images per GPU
 (BASELINE.json configs[2]; the metric BASELINE.json names).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline
+images/sec and ms_per_step).  --full adds everything measured in runs of its own: the W-MSA and
+GEMM rooflines, the exchange timing (`comm`, world > 1) and the CPU baseline described below.
+--dump-outputs DIR writes what the last timed step returned (snapshot_outputs) as DIR/<name>.npy;
+weights, images, labels and DropPath draws are seeded, so the same arguments give the same inputs.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N ranks itself
 (torch.distributed.run on 127.0.0.1 as a child process, before anything touches the GPU) and
@@ -48,6 +54,13 @@ def parse():
     ap.add_argument("--batch", type=int, default=256, help="images per GPU")
     ap.add_argument("--model", default="swinv2_tiny_window7_224")
     ap.add_argument("--loss", default="hxe", choices=["hxe", "multitask", "ce"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the kernel-timer rooflines "
+                         "(--no-roofline), the exchange timing (--comm-steps) and the CPU baseline "
+                         "(--cpu-baseline); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, logits, a seeded sample of the "
+                         "updated parameters) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-baseline", type=int, default=1)
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-roofline", action="store_true")
@@ -116,6 +129,41 @@ def synthetic_batch(args, tax, rank, device, img=224):
         if args.loss == "hxe":
             y = y.contiguous()
     return x, y
+
+
+DUMP_LOGIT_ENTRIES = 12 * 2**20  # 48 MiB of float32 over the logit tensors; the whole dump stays < 64 MB
+DUMP_PARAM_ENTRIES = 4096        # entries kept of each parameter tensor
+
+
+def _sampled(t, cap, seed):
+    """`t` as a float32 numpy array: whole (its own shape) up to `cap` entries, else a fixed
+    sample of `cap` of them (sorted flat indices drawn from default_rng(seed))."""
+    a = t.detach().float()
+    if a.numel() > cap:
+        idx = np.sort(np.random.default_rng(seed).choice(a.numel(), cap, replace=False))
+        a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+    return a.cpu().numpy()
+
+
+def snapshot_outputs(loss, trainer):
+    """What a caller of the timed step holds after it, as {name: float32 array}: the loss it
+    returned, the logits it left in trainer.state.outputs (one array per head), and the
+    parameters it updated (DUMP_PARAM_ENTRIES seeded entries of each, concatenated in
+    named_parameters order).  Taken right after the timed steps, before any extra ones."""
+    out = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+    logits = trainer.state.outputs
+    logits = list(logits) if isinstance(logits, (list, tuple)) else [logits]
+    for i, t in enumerate(logits):
+        out["logits" if len(logits) == 1 else f"logits_{i}"] = _sampled(t, DUMP_LOGIT_ENTRIES // len(logits), i)
+    out["params_sample"] = np.concatenate([_sampled(p, DUMP_PARAM_ENTRIES, 1000 + i).reshape(-1)
+                                           for i, p in enumerate(trainer.model.parameters())])
+    return out
+
+
+def dump_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 TRAFFIC_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bench_traffic.json")
@@ -366,14 +414,18 @@ def main():
         # side stream staying at the default: the input-gradient chain dispatches first
         torch.cuda.set_stream(torch.cuda.Stream(device=device, priority=args.stream_priority))
 
+    # the same arguments give the same run: one seed for the initial weights on every rank, then
+    # a rank's own for its DropPath draws (the batch has its own generators, synthetic_batch)
+    torch.manual_seed(42)
     cfg, tax, model, trainer = build(args, device)
+    torch.manual_seed(42 + rank)
     if args.steps_in_flight >= 0:
         trainer.max_steps_in_flight = args.steps_in_flight or None
     img = model.module.patch_embed.img_size[0]
     batch = synthetic_batch(args, tax, rank, device, img)
 
     work = wmsa_work(model.module, args.batch)
-    timing = not args.no_roofline
+    timing = args.full and not args.no_roofline
     timer, timed_steps, launches = None, args.steps, None
     if args.graph:
         # eager warm-up; the last roofline_steps of it carry the W-MSA kernel timer (graph
@@ -406,6 +458,7 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    dumped = snapshot_outputs(loss, trainer) if args.dump_outputs and rank == 0 else None
     fallbacks = ops.library_fallbacks(reset=True)  # warm-up + timed steps
     # caching-allocator health over the warm-up + timed steps: a step that needs more than the
     # card holds makes the allocator free its cache and retry (a device-wide sync per retry)
@@ -415,7 +468,7 @@ def main():
               "alloc_retries": int(ms.get("num_alloc_retries", 0)), "device_allocs": int(ms.get("num_device_alloc", 0)),
               "device_frees": int(ms.get("num_device_free", 0))}
     comm = None
-    if world > 1 and not args.graph and args.comm_steps > 0:
+    if args.full and world > 1 and not args.graph and args.comm_steps > 0:
         # the exchange's exposed time and each bucket's overlap window, on extra steps after the
         # timed region (Trainer.comm_timing: marks at the backward's start / end, each all-reduce
         # enqueue, and after buckets.synchronize())
@@ -568,8 +621,10 @@ def main():
         if gemm_shapes:
             mf["shapes"], mf["binding"] = shape_table(gemm_shapes, gemm_steps)
         result["mfma"] = mf
-    if rank == 0 and world == 1 and args.cpu_baseline and default_cfg:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline and default_cfg:
         result["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
     if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:

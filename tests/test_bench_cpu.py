@@ -70,3 +70,45 @@ def test_stage_breakdown_groups_launches_by_block_resolution():
     sb = bench.stage_breakdown(net, 256, bwd, 16, backward=True)
     assert [g["avg_launch_us"] for g in sb] == per_stage_us
     assert bench.stage_breakdown(net, 256, fwd[:5], 8, backward=False) is None
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    """Without --full the bench times its steps and nothing else; --dump-outputs is off."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_sample_is_fixed_and_float32(tmp_path):
+    """--dump-outputs: a tensor within the cap is written whole in its own shape, a larger one as
+    the same sorted seeded sample on every call; one float32 .npy per name."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    t = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    whole = bench._sampled(t, 1000, 0)
+    assert whole.shape == (10, 100) and whole.dtype == np.float32 and whole[3, 7] == 307
+    s1, s2 = bench._sampled(t, 64, 3), bench._sampled(t, 64, 3)
+    assert s1.shape == (64,) and np.array_equal(s1, s2) and (np.diff(s1) > 0).all()
+    assert not np.array_equal(s1, bench._sampled(t, 64, 4))
+    lin = torch.nn.Linear(3, 2)
+    heads = [torch.ones(4, 5), torch.zeros(4, 6, dtype=torch.bfloat16)]
+    trainer = types.SimpleNamespace(state=types.SimpleNamespace(outputs=heads), model=lin)
+    out = bench.snapshot_outputs(torch.tensor(2.5, dtype=torch.float64), trainer)
+    assert sorted(out) == ["logits_0", "logits_1", "loss", "params_sample"]
+    assert out["loss"].tolist() == [2.5] and out["logits_1"].shape == (4, 6)
+    want = np.concatenate([p.detach().numpy().reshape(-1) for p in lin.parameters()])
+    assert np.array_equal(out["params_sample"], want)
+    trainer.state.outputs = heads[0]
+    assert "logits" in bench.snapshot_outputs(torch.tensor(0.0), trainer)
+    bench.dump_outputs(str(tmp_path / "d"), out)
+    for name, a in out.items():
+        b = np.load(str(tmp_path / "d" / (name + ".npy")))
+        assert b.dtype == np.float32 and np.array_equal(a, b)

@@ -195,14 +195,13 @@ def test_hxe_oracle_closed_form_known_answers():
 
 def test_config_layering_and_reference_yaml():
     from hvamd import configs
-    ref_yaml = "/root/reference/configs/pretrain/r50_multitask_base.yaml"
-    layers = [ref_yaml] if os.path.exists(ref_yaml) else []
-    cfg = configs.load_config(*layers, overrides={"model": {"name": "swinv2_tiny_window7_224"},
-                                                  "hierarchy": {"variant": "hxe"}})
+    # the reference's configs/pretrain/r50_multitask_base.yaml, stored with the goldens
+    ref_yaml = os.path.join(ROOT, "tests", "golden", "r50_multitask_base.yaml")
+    cfg = configs.load_config(ref_yaml, overrides={"model": {"name": "swinv2_tiny_window7_224"},
+                                                   "hierarchy": {"variant": "hxe"}})
     assert cfg.model.name == "swinv2_tiny_window7_224" and cfg.hierarchy.variant == "hxe"
     assert cfg.optim.name == "DecoupledSGDW" and cfg.seed == 42
-    if layers:
-        assert cfg.hierarchy.multitask_coeffs == [8, 5.65, 4, 2.82, 2, 1.41, 1]
+    assert cfg.hierarchy.multitask_coeffs == [8, 5.65, 4, 2.82, 2, 1.41, 1]
     with pytest.raises(KeyError):
         configs.merge(configs.Config(), {"model": {"loss_name": "x"}})
     cfg = configs.merge(configs.Config(), {"algorithms": [{"cls": "LabelSmoothing",

@@ -8,7 +8,7 @@ mkdir -p $O
 for rep in $(seq 1 ${REPS:-2}); do
   for arm in A B; do
     if [ $arm = A ]; then args="$AB_A"; else args="$AB_B"; fi
-    timeout -k 10 300 python bench.py --cpu-baseline 0 $args > $O/b.json 2> $O/b.err || { tail -20 $O/b.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --cpu-baseline 0 $args > $O/b.json 2> $O/b.err || { tail -20 $O/b.err; exit 1; }
     python3 -c "
 import json; d=json.load(open('$O/b.json'))
 f=[(s['avg_launch_us'], s['frac']) for s in d['roofline']['stages']]; b=[(s['avg_launch_us'], s['frac']) for s in d['roofline_bwd']['stages']]

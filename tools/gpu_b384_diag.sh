@@ -6,7 +6,7 @@ O=gpurun_out/${DIAG_OUT:-b384diag}
 mkdir -p $O
 run() {  # name args...
   local n=$1; shift
-  timeout -k 10 300 python bench.py --model swinv2_base_window24_384 --loss hxe --steps 5 --warmup 2 --cpu-baseline 0 "$@" > $O/$n.json 2> $O/$n.err || { tail -20 $O/$n.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --model swinv2_base_window24_384 --loss hxe --steps 5 --warmup 2 --cpu-baseline 0 "$@" > $O/$n.json 2> $O/$n.err || { tail -20 $O/$n.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$O/$n.json')); print('$n', d['value'], d['ms_per_step'], d.get('memory'), d['library_fallbacks'])"
 }

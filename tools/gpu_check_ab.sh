@@ -12,7 +12,7 @@ tail -1 $O/smoke.log
 for rep in $(seq 1 ${REPS:-2}); do
   for arm in A B; do
     if [ $arm = A ]; then args="$AB_A"; else args="$AB_B"; fi
-    timeout -k 10 300 python bench.py --cpu-baseline 0 $args > $O/b$arm$rep.json 2> $O/b$arm$rep.err || { tail -20 $O/b$arm$rep.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --cpu-baseline 0 $args > $O/b$arm$rep.json 2> $O/b$arm$rep.err || { tail -20 $O/b$arm$rep.err; exit 1; }
     echo "$arm [$args] $(python3 -c "
 import json; d=json.load(open('$O/b$arm$rep.json')); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline_bwd']['frac'], d['mfma']['binding']['all'])")"
   done

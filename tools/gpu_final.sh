@@ -8,10 +8,10 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -2 $O/tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json
-timeout -k 10 400 python bench.py --model swinv2_base_window7_224 --loss multitask --steps 10 --warmup 3 > $O/b224.json 2> $O/b224.err || { tail -20 $O/b224.err; exit 1; }
-timeout -k 10 600 python bench.py --model swinv2_base_window24_384 --loss hxe --steps 5 --warmup 2 > $O/b384.json 2> $O/b384.err || { tail -20 $O/b384.err; exit 1; }
+timeout -k 10 400 python bench.py --full --model swinv2_base_window7_224 --loss multitask --steps 10 --warmup 3 > $O/b224.json 2> $O/b224.err || { tail -20 $O/b224.err; exit 1; }
+timeout -k 10 600 python bench.py --full --model swinv2_base_window24_384 --loss hxe --steps 5 --warmup 2 > $O/b384.json 2> $O/b384.err || { tail -20 $O/b384.err; exit 1; }
 python3 -c "
 import json
 for f in ('b224', 'b384'):
