@@ -69,7 +69,8 @@ def smooth_labels(logits: torch.Tensor, target: torch.Tensor, smoothing: float =
 class LabelSmoothing(Algorithm):
     """Label smoothing that also handles multitask list outputs (algorithmic.py:88-119):
     BEFORE_LOSS swaps the targets for smoothed probability targets (one per tier
-    for list outputs); AFTER_LOSS restores the originals."""
+    for list outputs; for one logit tensor with [B, tiers] taxonomy labels, the HXE
+    variant, the smoothed leaf column); AFTER_LOSS restores the originals."""
 
     def __init__(self, smoothing=0.1, target_key=1):
         self.smoothing = smoothing
@@ -89,6 +90,10 @@ class LabelSmoothing(Algorithm):
                 assert len(state.outputs) == tiers, "different level of tiers"
                 assert all(o.shape[0] == b for o in state.outputs), "different batch sizes"
                 smoothed = [smooth_labels(o, t, self.smoothing) for o, t in zip(state.outputs, labels.T)]
+            elif labels.ndim == 2 and not labels.dtype.is_floating_point:
+                # [B, tiers] taxonomy labels on leaf logits (the HXE variant): the leaf id is the
+                # finest tier's id, i.e. the logit column -> one [B, L] probability target
+                smoothed = smooth_labels(state.outputs, labels[:, -1], self.smoothing)
             else:
                 smoothed = smooth_labels(state.outputs, labels, self.smoothing)
             state.batch_set_item(self.target_key, smoothed)

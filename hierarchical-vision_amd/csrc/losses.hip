@@ -9,6 +9,9 @@
 //   leaf ranges of the target's ancestors, each range contiguous in `perm` order.
 //   One workgroup per sample; every range is a strided wavefront scan with an
 //   online (max, sum) pair and a cross-wave merge.
+// * HXE with soft targets (LabelSmoothing on the HXE variant): the expectation of the hard
+//   loss under a leaf weight vector; every node's LSE and weight sum, bottom-up over
+//   rank-ordered node slots, one workgroup per sample; the backward is one pass over the leaves.
 #include "hvk_common.h"
 
 namespace {
@@ -185,6 +188,132 @@ __global__ __launch_bounds__(256) void hxe_bwd_kernel(HxeArgs a) {
   }
 }
 
+// ----------------------------------------------------------------- HXE, soft targets
+// The expectation of the hard loss under a non-negative leaf weight vector t (include/hvk.h):
+// every internal node n needs LSE(n) and T(n) = sum of t over its leaves.  Nodes are indexed by
+// slot = rank_off[tier] + rank of the node within its tier by node_start (slot n_nodes = the
+// root), so the children of a slot are one contiguous range [child_lo, child_hi): permuted leaf
+// positions for tier 5, slots of the next finer tier above it.  The forward works bottom-up, one
+// workgroup per sample: tier 5 reduces its leaves, each coarser tier merges its children's
+// (LSE, T) from the saved [B, n_nodes + 1] buffers, a barrier between tiers.  Every node keeps
+// its own running max; there are no atomics and every reduction has a fixed order.
+struct HxeSoftArgs {
+  const float* logits; const float* soft; int B, L, n_nodes; const int* perm;
+  const int* rank_off; const int* child_lo; const int* child_hi; const int* anc;
+  const float* coeff; float* row_loss; float* node_lse; float* node_t;
+  const float* gout; float* dlogits;
+};
+
+// a node with at most this many children is reduced by one lane, a wider one by its whole wave
+constexpr int kSerialWidth = 16;
+
+// children first, first + step, ... < hi of one node folded into (acc, T); tz += t_k z_k (leaves)
+template <bool LEAVES>
+__device__ __forceinline__ void soft_children(const HxeSoftArgs& a, const float* z, const float* t,
+                                              const float* nl, const float* nt, int first, int hi,
+                                              int step, Lse& acc, float& T, float& tz) {
+  for (int c = first; c < hi; c += step) {
+    if (LEAVES) {
+      const int k = a.perm ? a.perm[c] : c;
+      const float x = z[k], w = t[k];
+      acc = lse_push(acc, x);
+      T += w;
+      tz += w * x;
+    } else {
+      acc = lse_merge(acc, Lse{nl[c], 1.f});
+      T += nt[c];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void hxe_soft_fwd_kernel(HxeSoftArgs a) {
+  __shared__ float sred[2][4];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float* z = a.logits + (size_t)b * a.L;
+  const float* t = a.soft + (size_t)b * a.L;
+  // written and read back in this kernel (by other waves, across the tier barrier): no restrict
+  float* nl = a.node_lse + (size_t)b * (a.n_nodes + 1);
+  float* nt = a.node_t + (size_t)b * (a.n_nodes + 1);
+  float part = 0.f;  // this thread's share of sum_n c_l T(n) LSE(n)
+  float tz = 0.f;    // ... and of sum_k t_k z_k
+  for (int s = 0; s < kTiers; ++s) {
+    const int q = s < kTiers - 1 ? kTiers - 2 - s : kTiers - 1;  // tiers 5 .. 0, then 6 = the root
+    const int n0 = a.rank_off[q], n1 = a.rank_off[q + 1];
+    const float cl = a.coeff[q < kTiers - 1 ? kTiers - 1 - q : kLevels - 1];
+    for (int base = n0 + wv * 64; base < n1; base += 256) {  // wave-uniform: 64 slots per wave
+      const int i = base + lane;
+      int lo = 0, hi = 0;
+      if (i < n1) {
+        lo = a.child_lo[i];
+        hi = a.child_hi[i];
+      }
+      const bool wide = hi - lo > kSerialWidth;
+      if (i < n1 && !wide) {
+        Lse acc{-INFINITY, 0.f};
+        float T = 0.f;
+        if (q == kTiers - 2) soft_children<true>(a, z, t, nl, nt, lo, hi, 1, acc, T, tz);
+        else soft_children<false>(a, z, t, nl, nt, lo, hi, 1, acc, T, tz);
+        const float v = acc.m + __logf(acc.s);
+        nl[i] = v;
+        nt[i] = T;
+        if (T != 0.f) part += cl * T * v;
+      }
+      unsigned long long m = __ballot(wide);
+      while (m) {  // the wave's wide nodes, one after the other, 64 lanes strided over the children
+        const int j = __ffsll(m) - 1;
+        m &= m - 1;
+        const int jlo = __shfl(lo, j), jhi = __shfl(hi, j);
+        Lse acc{-INFINITY, 0.f};
+        float T = 0.f;
+        if (q == kTiers - 2) soft_children<true>(a, z, t, nl, nt, jlo + lane, jhi, 64, acc, T, tz);
+        else soft_children<false>(a, z, t, nl, nt, jlo + lane, jhi, 64, acc, T, tz);
+        acc = wave_lse(acc);
+        T = hvk_wave_sum(T);
+        if (lane == 0) {
+          const float v = acc.m + __logf(acc.s);
+          nl[base + j] = v;
+          nt[base + j] = T;
+          if (T != 0.f) part += cl * T * v;
+        }
+      }
+    }
+    __syncthreads();  // the next tier reads these (LSE, T) back (workgroup-scope release / acquire)
+  }
+  part = hvk_wave_sum(part);
+  tz = hvk_wave_sum(tz);
+  if (lane == 0) {
+    sred[0][wv] = part;
+    sred[1][wv] = tz;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      part += sred[0][w];
+      tz += sred[1][w];
+    }
+    a.row_loss[b] = a.coeff[0] * tz + part;
+  }
+}
+
+// one thread per permuted position: the six ancestors' (LSE, T) through anc [L, 6], plus the root
+__global__ __launch_bounds__(256) void hxe_soft_bwd_kernel(HxeSoftArgs a, int chunks) {
+  const int b = blockIdx.x / chunks;
+  const int pos = (blockIdx.x - b * chunks) * 256 + threadIdx.x;
+  if (pos >= a.L) return;
+  const float* __restrict__ nl = a.node_lse + (size_t)b * (a.n_nodes + 1);
+  const float* __restrict__ nt = a.node_t + (size_t)b * (a.n_nodes + 1);
+  const int k = a.perm ? a.perm[pos] : pos;
+  const float x = a.logits[(size_t)b * a.L + k];
+  float d = a.coeff[0] * a.soft[(size_t)b * a.L + k];
+#pragma unroll
+  for (int q = 0; q < kTiers; ++q) {
+    const int i = q < kTiers - 1 ? a.anc[(size_t)pos * (kTiers - 1) + q] : a.n_nodes;
+    const float T = nt[i];
+    if (T != 0.f) d += a.coeff[q < kTiers - 1 ? kTiers - 1 - q : kLevels - 1] * T * __expf(x - nl[i]);
+  }
+  a.dlogits[(size_t)b * a.L + k] = a.gout[0] / a.B * d;
+}
+
 }  // namespace
 
 extern "C" {
@@ -243,6 +372,42 @@ int hvk_hxe_bwd(const float* logits, int B, int L, const int* perm, const int64_
             nullptr, const_cast<float*>(lse), grad_out, dlogits};
   hipLaunchKernelGGL(hxe_bwd_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   HVK_CHECK_LAUNCH("hxe_bwd");
+  return HVK_OK;
+}
+
+int hvk_hxe_soft_fwd(const float* logits, const float* soft, int B, int L, const int* perm,
+                     int n_nodes, const int* rank_off, const int* child_lo, const int* child_hi,
+                     const float* level_coeff, float* row_loss, float* node_lse, float* node_t,
+                     void* stream) {
+  if (!logits || !soft || !rank_off || !child_lo || !child_hi || !level_coeff || !row_loss ||
+      !node_lse || !node_t)
+    return hvk_set_error(HVK_EINVAL, "hvk_hxe_soft_fwd: null pointer");
+  if (B <= 0 || L <= 0 || n_nodes <= 0)
+    return hvk_set_error(HVK_EINVAL, "hvk_hxe_soft_fwd: bad shape");
+  HxeSoftArgs a{logits, soft, B, L, n_nodes, perm, rank_off, child_lo, child_hi, nullptr,
+                level_coeff, row_loss, node_lse, node_t, nullptr, nullptr};
+  hipLaunchKernelGGL(hxe_soft_fwd_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     a);
+  HVK_CHECK_LAUNCH("hxe_soft_fwd");
+  return HVK_OK;
+}
+
+int hvk_hxe_soft_bwd(const float* logits, const float* soft, int B, int L, const int* perm,
+                     int n_nodes, const int* anc, const float* level_coeff, const float* node_lse,
+                     const float* node_t, const float* grad_out, float* dlogits, void* stream) {
+  if (!logits || !soft || !anc || !level_coeff || !node_lse || !node_t || !grad_out || !dlogits)
+    return hvk_set_error(HVK_EINVAL, "hvk_hxe_soft_bwd: null pointer");
+  if (B <= 0 || L <= 0 || n_nodes <= 0)
+    return hvk_set_error(HVK_EINVAL, "hvk_hxe_soft_bwd: bad shape");
+  const int chunks = (L + 255) / 256;
+  if ((long long)B * chunks > 0x7fffffffLL)
+    return hvk_set_error(HVK_EINVAL, "hvk_hxe_soft_bwd: B * ceil(L / 256) exceeds the grid");
+  HxeSoftArgs a{logits, soft, B, L, n_nodes, perm, nullptr, nullptr, nullptr, anc, level_coeff,
+                nullptr, const_cast<float*>(node_lse), const_cast<float*>(node_t), grad_out,
+                dlogits};
+  hipLaunchKernelGGL(hxe_soft_bwd_kernel, dim3(B * chunks), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), a, chunks);
+  HVK_CHECK_LAUNCH("hxe_soft_bwd");
   return HVK_OK;
 }
 

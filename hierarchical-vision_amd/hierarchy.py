@@ -3,7 +3,10 @@
 Host-side integer work (label parsing, tier-id assignment, parent lookup, the
 leaf permutation that makes every taxonomy node a contiguous leaf range) is
 plain Python/numpy and bit-exact with the reference.  The losses run as HIP
-kernels (ops.multitask_cross_entropy, ops.hierarchical_cross_entropy).
+kernels (ops.multitask_cross_entropy, ops.hierarchical_cross_entropy and, for
+probability targets over the leaves such as LabelSmoothing's,
+ops.hierarchical_cross_entropy_soft: the expectation of the hard HXE loss, over
+the rank-ordered node tables of Taxonomy.soft_tables()).
 """
 import collections
 import dataclasses
@@ -165,6 +168,8 @@ class Taxonomy:
         self.node_end = np.concatenate(ends).astype(np.int32)
         self.tier_base = np.r_[0, np.cumsum(self.num_classes)[:-1]].astype(np.int32)
         self._dev = {}
+        self._soft = None
+        self._soft_dev = {}
 
     @property
     def num_leaves(self):
@@ -196,6 +201,57 @@ class Taxonomy:
             self._dev[key] = (None if self.identity_perm else mk(self.perm), mk(self.node_start),
                               mk(self.node_end), mk(self.tier_base), mk(self.leaf_paths))
         return self._dev[key]
+
+    def soft_tables(self):
+        """The node-slot tables of the soft-target HXE kernels (numpy int32, built once).
+
+        The internal nodes of tier t (0..5) are ranked by node_start; the node of rank r has
+        slot rank_off[t] + r, the root slot n_nodes = rank_off[6] (rank_off[7] = n_nodes + 1).
+        Returns (rank_off [8], child_lo, child_hi [n_nodes + 1], anc [L, 6], slot_node
+        [n_nodes]): the children of slot i are [child_lo[i], child_hi[i]) -- permuted leaf
+        positions for tier 5, slots of the next finer tier above it (the root's are tier 0);
+        anc[p, t] is the slot of the tier-t ancestor of permuted position p; slot_node[i] is
+        the tier id of the node in slot i (host side only)."""
+        if self._soft is None:
+            tiers = N_TIERS - 1
+            rank_off = np.r_[0, np.cumsum(self.num_classes[:tiers])]
+            n_nodes = int(rank_off[-1])
+            rank_off = np.r_[rank_off, n_nodes + 1]
+            ordered = self.leaf_paths[self.perm]
+            child_lo = np.zeros(n_nodes + 1, np.int64)
+            child_hi = np.zeros(n_nodes + 1, np.int64)
+            anc = np.zeros((self.num_leaves, tiers), np.int64)
+            slot_node = np.zeros(n_nodes, np.int64)
+            finer = None  # sorted starts of the next finer tier
+            for t in range(tiers - 1, -1, -1):
+                n = self.num_classes[t]
+                st = self.node_start[self.tier_base[t]:self.tier_base[t] + n].astype(np.int64)
+                en = self.node_end[self.tier_base[t]:self.tier_base[t] + n].astype(np.int64)
+                order = np.argsort(st, kind="stable")  # rank -> node id
+                rank = np.empty(n, np.int64)
+                rank[order] = np.arange(n)
+                sl = slice(rank_off[t], rank_off[t + 1])
+                slot_node[sl] = order
+                if finer is None:
+                    child_lo[sl], child_hi[sl] = st[order], en[order]
+                else:  # ranges nest: the children are the finer nodes that start inside
+                    child_lo[sl] = rank_off[t + 1] + np.searchsorted(finer, st[order])
+                    child_hi[sl] = rank_off[t + 1] + np.searchsorted(finer, en[order])
+                anc[:, t] = rank_off[t] + rank[ordered[:, t]]
+                finer = st[order]
+            child_lo[n_nodes], child_hi[n_nodes] = rank_off[0], rank_off[1]
+            self._soft = tuple(a.astype(np.int32) for a in (rank_off, child_lo, child_hi, anc,
+                                                             slot_node))
+        return self._soft
+
+    def device_soft_tables(self, device):
+        """(perm or None, rank_off, child_lo, child_hi, anc) of soft_tables() on `device`."""
+        key = str(device)
+        if key not in self._soft_dev:
+            mk = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+            self._soft_dev[key] = (None if self.identity_perm else mk(self.perm),
+                                   *(mk(a) for a in self.soft_tables()[:4]))
+        return self._soft_dev[key]
 
 
 def hxe_level_coeffs(tree_weights="uniform", alpha=0.1):
@@ -289,7 +345,9 @@ class HierarchicalCrossEntropy(torch.nn.Module):
     stubs it (hierarchy.py:183-185) and exposes the knobs hxe_tree_weights /
     hxe_alpha (configs.py:93-96): parity unpinned, pinned by closed-form tests.
 
-    forward(logits [B, n_leaves], targets [B, 7] tier ids or [B] leaf ids)."""
+    forward(logits [B, n_leaves], targets [B, 7] tier ids or [B] leaf ids), or floating-point
+    targets [B, n_leaves]: non-negative leaf weights t (LabelSmoothing's smoothed leaf column),
+    the loss then being the expectation sum_c t_c L(c) of the hard loss."""
 
     def __init__(self, taxonomy: Taxonomy, tree_weights="uniform", alpha=0.1):
         super().__init__()
@@ -297,8 +355,16 @@ class HierarchicalCrossEntropy(torch.nn.Module):
         self.register_buffer("level_coeff", hxe_level_coeffs(tree_weights, alpha))
 
     def forward(self, logits, targets):
-        if isinstance(targets, list) or targets.dtype.is_floating_point:
-            raise NotImplementedError("HXE takes hard taxonomy targets (no label smoothing)")
+        if isinstance(targets, list):
+            raise NotImplementedError("HXE takes one target tensor over the leaves, not a "
+                                      "per-tier list (that is the multitask loss's form)")
+        if targets.dtype.is_floating_point:
+            if targets.shape != logits.shape:
+                raise ValueError(f"soft HXE targets {tuple(targets.shape)} != logits "
+                                 f"{tuple(logits.shape)}")
+            perm, rank_off, lo, hi, anc = self.taxonomy.device_soft_tables(logits.device)
+            return ops.hierarchical_cross_entropy_soft(logits, targets, perm, rank_off, lo, hi,
+                                                       anc, self.level_coeff)
         perm, start, end, base, paths = self.taxonomy.device_tables(logits.device)
         if targets.ndim == 1:
             targets = paths[targets]

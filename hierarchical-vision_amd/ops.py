@@ -1791,3 +1791,49 @@ class HierarchicalCE(torch.autograd.Function):
 def hierarchical_cross_entropy(logits, targets, perm, node_start, node_end, tier_base, level_coeff):
     return HierarchicalCE.apply(logits, targets.to(torch.int64).contiguous(), perm, node_start,
                                 node_end, tier_base, level_coeff)
+
+
+class HierarchicalSoftCE(torch.autograd.Function):
+    """HXE over leaf logits [B, L] with non-negative leaf weights [B, L] as the target: the
+    expectation of the hard loss; see include/hvk.h for the definition and the tables.  Also
+    returns the per-node (LSE, T) buffers [B, n_nodes + 1] the backward reads."""
+
+    @staticmethod
+    def forward(ctx, logits, soft, perm, rank_off, child_lo, child_hi, anc, level_coeff):
+        logits = _f32(logits)
+        B, L = logits.shape
+        n_nodes = child_lo.numel() - 1
+        row_loss = torch.empty(B, device=logits.device, dtype=torch.float32)
+        node_lse = torch.empty((B, n_nodes + 1), device=logits.device, dtype=torch.float32)
+        node_t = torch.empty((B, n_nodes + 1), device=logits.device, dtype=torch.float32)
+        call("hvk_hxe_soft_fwd", ptr(logits), ptr(soft), B, L, ptr(perm), n_nodes, ptr(rank_off),
+             ptr(child_lo), ptr(child_hi), ptr(level_coeff), ptr(row_loss), ptr(node_lse),
+             ptr(node_t), stream())
+        ctx.save_for_backward(logits, soft, perm, anc, level_coeff, node_lse, node_t)
+        ctx.has_perm = perm is not None
+        ctx.mark_non_differentiable(node_lse, node_t)
+        return row_loss.mean(), node_lse, node_t
+
+    @staticmethod
+    def backward(ctx, gout, _glse, _gt):
+        logits, soft, perm, anc, level_coeff, node_lse, node_t = ctx.saved_tensors
+        B, L = logits.shape
+        dlogits = torch.empty_like(logits)
+        gout = _f32(gout.reshape(1))
+        call("hvk_hxe_soft_bwd", ptr(logits), ptr(soft), B, L, ptr(perm if ctx.has_perm else None),
+             node_lse.shape[1] - 1, ptr(anc), ptr(level_coeff), ptr(node_lse), ptr(node_t),
+             ptr(gout), ptr(dlogits), stream())
+        return dlogits, None, None, None, None, None, None, None
+
+
+def hierarchical_cross_entropy_soft(logits, soft, perm, rank_off, child_lo, child_hi, anc,
+                                    level_coeff, return_nodes=False):
+    """Soft-target HXE (tables: hierarchy.Taxonomy.device_soft_tables).  return_nodes: also the
+    forward's per-node LSE and T buffers."""
+    if soft.shape != logits.shape or logits.ndim != 2:
+        raise ValueError(f"soft targets {tuple(soft.shape)} != logits {tuple(logits.shape)}")
+    if anc.shape != (logits.shape[1], 6) or child_hi.numel() != child_lo.numel():
+        raise ValueError("taxonomy tables do not fit the logits")
+    loss, node_lse, node_t = HierarchicalSoftCE.apply(logits, _f32(soft.detach()), perm, rank_off,
+                                                      child_lo, child_hi, anc, level_coeff)
+    return (loss, node_lse, node_t) if return_nodes else loss

@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 14
+#define HVK_ABI_VERSION 15
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -477,6 +477,31 @@ int hvk_hxe_bwd(const float* logits, int B, int L, const int* perm, const int64_
                 const int* node_start, const int* node_end, const int* tier_base,
                 const float* level_coeff, const float* lse, const float* grad_out,
                 float* dlogits, void* stream);
+
+/* ---- HXE with soft targets (LabelSmoothing on the hierarchical loss) -------------
+ * soft: f32 [B, L] non-negative leaf weights t (any sum; an all-zero row gives zero loss and
+ * gradient).  The loss is the expectation of the hard loss, L_b = sum_c t_c L(c); a node's
+ * children partition it, so with T(n) = sum of t over the leaves of n
+ *   L_b = c_0 sum_k t_k z_k + sum_{l=1..6} c_l sum_{n in tier 6-l} T(n) LSE(n)
+ *       + c_7 (sum_k t_k) LSE_all,                                   c = level_coeff [8]
+ *   dL_b/dz_k = c_0 t_k + sum_{l=1..7} c_l T(a_l(k)) exp(z_k - LSE(a_l(k))),
+ * a_l(k) the level-l ancestor of leaf k.  A one-hot t gives hvk_hxe_fwd's loss.
+ * Nodes are addressed by slot: the nodes of tier t (0..5), ranked by node_start, occupy slots
+ * [rank_off[t], rank_off[t+1]); rank_off[6] = n_nodes is the root's slot and rank_off[7] =
+ * n_nodes + 1 (rank_off: int [8]).  The children of slot i are [child_lo[i], child_hi[i])
+ * (int [n_nodes + 1] each): permuted leaf positions for tier 5, slots of the next finer tier
+ * above it (the root's are tier 0).  anc: int [L, 6], the slot of the tier-t ancestor of
+ * permuted position p at anc[6 p + t].
+ * Forward: row_loss f32 [B]; node_lse, node_t f32 [B, n_nodes + 1] receive LSE(n) and T(n) of
+ * every slot, the state the backward reads.  Backward: dlogits = grad_out / B * dL_b/dz.
+ * No atomics: values are bit-identical from run to run. */
+int hvk_hxe_soft_fwd(const float* logits, const float* soft, int B, int L, const int* perm,
+                     int n_nodes, const int* rank_off, const int* child_lo, const int* child_hi,
+                     const float* level_coeff, float* row_loss, float* node_lse, float* node_t,
+                     void* stream);
+int hvk_hxe_soft_bwd(const float* logits, const float* soft, int B, int L, const int* perm,
+                     int n_nodes, const int* anc, const float* level_coeff, const float* node_lse,
+                     const float* node_t, const float* grad_out, float* dlogits, void* stream);
 
 #ifdef __cplusplus
 }
