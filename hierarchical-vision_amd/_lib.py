@@ -67,6 +67,9 @@ SIGNATURES = {
     "hvk_sgdw_workspace_bytes": (_sz, [_i, _p]),
     "hvk_sgdw_step": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _f, _f, _f, _f, _i, _i, _f, _p, _sz,
                            _p]),
+    "hvk_adamw_workspace_bytes": (_sz, [_i, _p]),
+    "hvk_adamw_step": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _f, _f, _f, _f, _f, _f, _i, _f, _p,
+                            _sz, _p]),
     "hvk_weight_grad_workspace": (_sz, [_i, _i, _i]),
     "hvk_weight_grad": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _sz, _p]),
     "hvk_weight_grad_shift": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _sz, _p]),
@@ -120,7 +123,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 15  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
+ABI_VERSION = 16  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
 
 
 def load():

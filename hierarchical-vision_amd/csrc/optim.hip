@@ -16,6 +16,9 @@
 //      with the products rounded in the same order as the torch foreach sequence.
 // lr / decay come from the kernel arguments or, for HIP-graph replays (trainer.py), from a
 // device array the host refreshes before each replay.
+// hvk_adamw_step is the same three launches with AdamW's update in the third (adamw_kernel: the
+// moments m, v and torch's foreach rounding order; the host folds the step count into step_size
+// and bc2_sqrt, so a captured launch is refreshed through the device array like lr / decay).
 // The tensor table (pointers, sizes, parameter group) travels in the kernel arguments, up to
 // kBatch tensors per launch (no device-side table to keep in sync with the autograd-owned
 // gradient buffers, and graph capture sees plain kernel nodes).
@@ -51,7 +54,34 @@ struct Groups {
   float decay[kMaxGroups];
 };
 
-__device__ __forceinline__ int find_entry(const Entry* t, int n, int chunk) {
+struct AdamEntry {  // one parameter tensor of the AdamW step: Entry + the second moment
+  float* p;
+  const float* g;
+  float* m;    // exp_avg
+  float* v;    // exp_avg_sq
+  float* ema;  // nullptr: no EMA this step
+  int n;
+  int chunk0;
+  int group;  // as Entry::group
+};
+
+struct AdamBatch {
+  AdamEntry e[kBatch];
+  int nt;
+};
+
+struct AdamHyper {  // the layout of the device `hyper` array (12 floats with its padding)
+  float step_size[kMaxGroups];  // lr / (1 - beta1^t)
+  float decay[kMaxGroups];
+  float bc2_sqrt;  // sqrt(1 - beta2^t)
+};
+// 56-B entries: 64 of them and every other argument of adamw_kernel (128 B at most) fit the
+// 4 KB kernel-argument block
+static_assert(sizeof(AdamEntry) == 56 && sizeof(AdamBatch) + sizeof(AdamHyper) + 128 <= 4096,
+              "adamw_kernel's arguments exceed the kernel-argument limit: lower kBatch");
+
+template <class E>
+__device__ __forceinline__ int find_entry(const E* t, int n, int chunk) {
   int lo = 0, hi = n - 1;  // last entry with chunk0 <= chunk
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -162,6 +192,73 @@ __global__ __launch_bounds__(kThreads) void sgdw_kernel(Batch b, const float* __
   }
 }
 
+// One element of torch's foreach AdamW (decay, lerp, second moment, addcdiv) with IEEE sqrt and
+// division; contraction off so that only the fmas written here fuse (both paths round alike).
+__device__ __forceinline__ void adamw1(float& p, float& m, float& v, float g, float coef, float w1,
+                                       float b2, float w2, float eps, float bc2, bool first,
+                                       float decay, float ss) {
+#pragma clang fp contract(off)
+  const float gc = g * coef;
+  const float mv = first ? w1 * gc : fmaf(gc - m, w1, m);
+  const float g2 = w2 * gc;
+  const float vv = first ? g2 * gc : fmaf(g2, gc, v * b2);
+  m = mv;
+  v = vv;
+  const float denom = sqrtf(vv) / bc2 + eps;
+  p = fmaf(-ss, mv / denom, p * decay);
+}
+
+__global__ __launch_bounds__(kThreads) void adamw_kernel(AdamBatch b, const float* __restrict__ coefp,
+                                                        float coef_host, AdamHyper hp,
+                                                        const float* __restrict__ hyper, float beta1,
+                                                        float beta2, float eps, int first,
+                                                        float ema_a) {
+  const AdamEntry e = b.e[find_entry(b.e, b.nt, blockIdx.x)];
+  const float coef = coefp ? *coefp : coef_host;
+  const int gi = e.group & 255;
+  const float ss = hyper ? hyper[gi] : hp.step_size[gi];
+  const float decay = hyper ? hyper[kMaxGroups + gi] : hp.decay[gi];
+  const float bc2 = hyper ? hyper[2 * kMaxGroups] : hp.bc2_sqrt;
+  const float w1 = 1.f - beta1, w2 = 1.f - beta2;
+  const long long c0 = (long long)(blockIdx.x - e.chunk0) * kChunk;
+  const long long c1 = c0 + kChunk < e.n ? c0 + kChunk : e.n;
+  const bool fst = first != 0;
+  if (e.group & 256) {
+    float4* p4 = reinterpret_cast<float4*>(e.p);
+    float4* m4 = reinterpret_cast<float4*>(e.m);
+    float4* v4 = reinterpret_cast<float4*>(e.v);
+    const float4* g4 = reinterpret_cast<const float4*>(e.g);
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 2
+    for (long long i = c0 / 4 + threadIdx.x; i < c1 / 4; i += kThreads) {
+      float4 p = p4[i], m = fst ? zero : m4[i], v = fst ? zero : v4[i];
+      const float4 g = g4[i];
+      adamw1(p.x, m.x, v.x, g.x, coef, w1, beta2, w2, eps, bc2, fst, decay, ss);
+      adamw1(p.y, m.y, v.y, g.y, coef, w1, beta2, w2, eps, bc2, fst, decay, ss);
+      adamw1(p.z, m.z, v.z, g.z, coef, w1, beta2, w2, eps, bc2, fst, decay, ss);
+      adamw1(p.w, m.w, v.w, g.w, coef, w1, beta2, w2, eps, bc2, fst, decay, ss);
+      p4[i] = p;
+      m4[i] = m;
+      v4[i] = v;
+      if (e.ema) {
+        float4* e4 = reinterpret_cast<float4*>(e.ema);
+        float4 q = e4[i];
+        ema1(q.x, p.x, ema_a); ema1(q.y, p.y, ema_a); ema1(q.z, p.z, ema_a); ema1(q.w, p.w, ema_a);
+        e4[i] = q;
+      }
+    }
+  } else {
+    for (long long i = c0 + threadIdx.x; i < c1; i += kThreads) {
+      float p = e.p[i], m = fst ? 0.f : e.m[i], v = fst ? 0.f : e.v[i];
+      adamw1(p, m, v, e.g[i], coef, w1, beta2, w2, eps, bc2, fst, decay, ss);
+      e.p[i] = p;
+      e.m[i] = m;
+      e.v[i] = v;
+      if (e.ema) ema1(e.ema[i], p, ema_a);
+    }
+  }
+}
+
 int chunks_of(long long n) { return (int)((n + kChunk - 1) / kChunk); }
 
 }  // namespace
@@ -231,6 +328,87 @@ int hvk_sgdw_step(int n, float* const* p, const float* const* g, float* const* m
     hipLaunchKernelGGL(sgdw_kernel, dim3(nch(b)), dim3(kThreads), 0, st, b, coefp, grad_scale, gp,
                        hyper, momentum, dampening, nesterov, first, ema_smoothing);
     HVK_CHECK_LAUNCH("hvk_sgdw_step");
+  }
+  return HVK_OK;
+}
+
+size_t hvk_adamw_workspace_bytes(int n, const long long* numel) {
+  return hvk_sgdw_workspace_bytes(n, numel);  // the same chunk slots + the clip coefficient
+}
+
+int hvk_adamw_step(int n, float* const* p, const float* const* g, float* const* m, float* const* v,
+                   float* const* ema, const long long* numel, const int* group,
+                   const float* step_size, const float* decay, int ngroups, const float* hyper,
+                   float grad_scale, float max_norm, float beta1, float beta2, float eps,
+                   float bc2_sqrt, int first, float ema_smoothing, float* workspace,
+                   size_t ws_bytes, void* stream) {
+  if (n <= 0) return HVK_OK;
+  if (!p || !g || !m || !v || !numel || !group || !step_size || !decay || !workspace)
+    return hvk_set_error(HVK_EINVAL, "hvk_adamw_step: null argument");
+  if (!(grad_scale > 0.f))
+    return hvk_set_error(HVK_EINVAL, "hvk_adamw_step: grad_scale %g", (double)grad_scale);
+  if (ngroups < 1 || ngroups > kMaxGroups)
+    return hvk_set_error(HVK_EINVAL, "hvk_adamw_step: %d parameter groups (max %d)", ngroups, kMaxGroups);
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
+    return hvk_set_error(HVK_EINVAL, "hvk_adamw_step: betas (%g, %g) outside [0, 1)", (double)beta1,
+                         (double)beta2);
+  if (!(eps > 0.f)) return hvk_set_error(HVK_EINVAL, "hvk_adamw_step: eps %g", (double)eps);
+  if (!hyper && !(bc2_sqrt > 0.f))
+    return hvk_set_error(HVK_EINVAL, "hvk_adamw_step: bc2_sqrt %g", (double)bc2_sqrt);
+  if (ws_bytes < hvk_adamw_workspace_bytes(n, numel))
+    return hvk_set_error(HVK_EINVAL, "hvk_adamw_step: workspace %zu B too small", ws_bytes);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t nb = (size_t)(n + kBatch - 1) / kBatch;
+  std::vector<AdamBatch> batches(nb);
+  std::vector<Batch> norm(max_norm > 0.f ? nb : 0);  // sumsq_kernel's view of the same tensors
+  int part = 0;
+  for (size_t bi = 0; bi < nb; ++bi) {
+    AdamBatch& b = batches[bi];
+    b.nt = n - (int)bi * kBatch < kBatch ? n - (int)bi * kBatch : kBatch;
+    int ch = 0;
+    for (int i = 0; i < b.nt; ++i) {
+      const int k = (int)bi * kBatch + i;
+      float* ek = ema ? ema[k] : nullptr;
+      if (!p[k] || !g[k] || !m[k] || !v[k] || (ema && !ek) || numel[k] <= 0 || numel[k] > (1ll << 30) ||
+          group[k] < 0 || group[k] >= ngroups)
+        return hvk_set_error(HVK_EINVAL, "hvk_adamw_step: tensor %d invalid", k);
+      const bool v4 = ((reinterpret_cast<size_t>(p[k]) | reinterpret_cast<size_t>(g[k]) |
+                        reinterpret_cast<size_t>(m[k]) | reinterpret_cast<size_t>(v[k]) |
+                        reinterpret_cast<size_t>(ek)) % 16 == 0) &&
+                      numel[k] % 4 == 0;
+      const int gf = group[k] | (v4 ? 256 : 0);
+      b.e[i] = AdamEntry{p[k], g[k], m[k], v[k], ek, (int)numel[k], ch, gf};
+      if (!norm.empty()) norm[bi].e[i] = Entry{p[k], g[k], m[k], ek, (int)numel[k], ch, gf};
+      ch += chunks_of(numel[k]);
+    }
+    if (!norm.empty()) {
+      norm[bi].nt = b.nt;
+      norm[bi].part0 = part;
+    }
+    part += ch;
+  }
+  AdamHyper hp;
+  for (int i = 0; i < kMaxGroups; ++i) {
+    hp.step_size[i] = i < ngroups ? step_size[i] : 0.f;
+    hp.decay[i] = i < ngroups ? decay[i] : 1.f;
+  }
+  hp.bc2_sqrt = bc2_sqrt;
+  auto nch = [](const AdamBatch& b) { return b.e[b.nt - 1].chunk0 + chunks_of(b.e[b.nt - 1].n); };
+  const float* coefp = nullptr;
+  if (max_norm > 0.f) {
+    for (size_t bi = 0; bi < nb; ++bi) {
+      hipLaunchKernelGGL(sumsq_kernel, dim3(nch(batches[bi])), dim3(kThreads), 0, st, norm[bi], workspace);
+      HVK_CHECK_LAUNCH("hvk_adamw_step (norm)");
+    }
+    hipLaunchKernelGGL(coef_kernel, dim3(1), dim3(kThreads), 0, st, workspace, part, max_norm,
+                       grad_scale);
+    HVK_CHECK_LAUNCH("hvk_adamw_step (coef)");
+    coefp = workspace + part;
+  }
+  for (const AdamBatch& b : batches) {
+    hipLaunchKernelGGL(adamw_kernel, dim3(nch(b)), dim3(kThreads), 0, st, b, coefp, grad_scale, hp,
+                       hyper, beta1, beta2, eps, first, ema_smoothing);
+    HVK_CHECK_LAUNCH("hvk_adamw_step");
   }
   return HVK_OK;
 }

@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 15
+#define HVK_ABI_VERSION 16
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -297,6 +297,30 @@ int hvk_sgdw_step(int n, float* const* p, const float* const* g, float* const* m
                   const float* decay, int ngroups, const float* hyper, float grad_scale,
                   float max_norm, float momentum, float dampening, int nesterov, int first,
                   float ema_smoothing, float* workspace, size_t ws_bytes, void* stream);
+
+/* ---- Fused AdamW step (DDP mean + gradient-norm clipping + AdamW + EMA) ----------------
+ * The AdamW counterpart of hvk_sgdw_step over the same tensor lists, with m[k] = exp_avg and
+ * v[k] = exp_avg_sq (torch.optim.AdamW's state; optim.py:16-44 builds torch / composer AdamW).
+ * coef as in hvk_sgdw_step (max_norm <= 0: coef = grad_scale), then per element
+ *   g' = coef g
+ *   m  = first ? (1 - beta1) g' : m + (g' - m) (1 - beta1)
+ *   v  = first ? (1 - beta2) g' g' : beta2 v + (1 - beta2) g' g'
+ *   p  = p decay[group];  p = p - step_size[group] m / (sqrt(v) / bc2_sqrt + eps)
+ *   ema = a ema + (1 - a) p                      (only with an ema table)
+ * rounded in the order of torch's foreach AdamW.  The HOST folds the step count in:
+ * step_size[g] = lr[g] / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t); decay[g] = 1 - lr wd
+ * (torch AdamW) or 1 - wd lr / initial_lr (composer DecoupledAdamW).  first != 0: m and v are
+ * not read (they may be uninitialised).  hyper: NULL, or a DEVICE f32 array [12] =
+ * step_size[0..3], decay[0..3], bc2_sqrt, 3 pad floats, read at run time instead of step_size /
+ * decay / bc2_sqrt (HIP-graph replays).  0 <= beta1, beta2 < 1, eps > 0.  g is not modified.
+ * workspace: f32, hvk_adamw_workspace_bytes(n, numel) bytes. */
+size_t hvk_adamw_workspace_bytes(int n, const long long* numel);
+int hvk_adamw_step(int n, float* const* p, const float* const* g, float* const* m, float* const* v,
+                   float* const* ema, const long long* numel, const int* group,
+                   const float* step_size, const float* decay, int ngroups, const float* hyper,
+                   float grad_scale, float max_norm, float beta1, float beta2, float eps,
+                   float bc2_sqrt, int first, float ema_smoothing, float* workspace,
+                   size_t ws_bytes, void* stream);
 
 /* ---- W-MSA block biases (swinv2.py:218-220, 262) --------------------------------------
  * Forward: qkv_bias[3C] = (q_bias or 0, 0, 0) and eff[C] = proj_bias (or 0) + proj_w v_bias
