@@ -120,10 +120,11 @@ SIGNATURES = {
     "hvk_hxe_bwd": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "hvk_hxe_soft_fwd": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "hvk_hxe_soft_bwd": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "hvk_eval_metrics": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None
-ABI_VERSION = 16  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
+ABI_VERSION = 17  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
 
 
 def load():

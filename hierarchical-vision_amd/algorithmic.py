@@ -26,6 +26,9 @@ class Event(enum.Enum):
     BEFORE_BACKWARD = "before_backward"
     AFTER_BACKWARD = "after_backward"
     BATCH_END = "batch_end"
+    EVAL_START = "eval_start"
+    EVAL_BATCH_END = "eval_batch_end"
+    EVAL_END = "eval_end"
 
 
 class State:
@@ -147,22 +150,42 @@ class EMA(Algorithm):
     On an update batch the average is handed to an optimizer that can fold it into its own
     pass over the weights (optim.DecoupledSGDW's fused step: ema = a ema + (1 - a) p with the
     freshly updated p, so the weights are not read again); otherwise, and in HIP-graph replays
-    (the captured update runs every step), it runs as foreach passes at BATCH_END."""
+    (the captured update runs every step), it runs as foreach passes at BATCH_END.
 
-    def __init__(self, half_life="100ba", update_interval="20ba", smoothing=None):
+    Evaluation (Trainer.eval) scores the averaged weights, the ones the recipe is judged by:
+    EVAL_START exchanges the VALUES of the parameters and their averages in place and EVAL_END
+    exchanges them back bit for bit.  No tensor is rebound, so every address stays what the fused
+    optimizers' pointer tables and captured graphs hold.  `eval_with_ema=False` evaluates the
+    training weights instead."""
+
+    def __init__(self, half_life="100ba", update_interval="20ba", smoothing=None, eval_with_ema=True):
         hl = int(str(half_life).rstrip("ba"))
         self.update_interval = int(str(update_interval).rstrip("ba"))
         self.smoothing = smoothing if smoothing is not None else math.exp(
             -math.log(2) * self.update_interval / hl)
         self.ema_params = None
+        self.eval_with_ema = eval_with_ema
         self._handed = False
+        self._swapped = False
 
     def match(self, event, state):
-        return event in (Event.AFTER_BACKWARD, Event.BATCH_END)
+        return event in (Event.AFTER_BACKWARD, Event.BATCH_END, Event.EVAL_START, Event.EVAL_END)
+
+    def _exchange(self, params):
+        tmp = [p.detach().clone() for p in params]
+        torch._foreach_copy_([p.detach() for p in params], self.ema_params)
+        torch._foreach_copy_(self.ema_params, tmp)
 
     @torch.no_grad()
     def apply(self, event, state, logger=None):
         params = [p for p in state.model.parameters()]
+        if event in (Event.EVAL_START, Event.EVAL_END):
+            start = event == Event.EVAL_START
+            if self.ema_params is not None and (self._swapped if not start
+                                                else self.eval_with_ema and not self._swapped):
+                self._exchange(params)
+                self._swapped = start
+            return
         if event == Event.AFTER_BACKWARD:
             self._handed = False
             if self.ema_params is None or (state.timestamp_batch + 1) % self.update_interval:

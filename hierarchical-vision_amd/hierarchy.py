@@ -474,6 +474,88 @@ class FineGrainedCrossEntropy(CrossEntropyMetric):
         super().update(preds[-1], targets[:, -1])
 
 
+class EvalMetrics(torch.nn.Module):
+    """acc@1, acc@topk, cross-entropy and tree distance (models.py:61-101) from ONE kernel pass
+    over the logits (ops.eval_metrics, hvk_eval_metrics): the fused counterpart of the metric
+    classes above, which each re-derive their answer from the logits on their own.
+
+    `tree_dists` (uint8 or f32 [L, L], build_tree_dist_matrix) or `taxonomy` gives "tree-dist";
+    a taxonomy compares the 7-tier paths instead of reading the L * L matrix (the same number)
+    and adds the per-tier top-1 accuracies.  Ties follow one rule: equal logits rank by index,
+    lowest first (a stable descending sort).
+
+    The running sums are `state`, 16 doubles on the device (layout: include/hvk.h); it is the
+    module's only state_dict entry.  update() launches and returns without a host
+    synchronisation, so it can be captured in a HIP graph (move the module to the device first);
+    compute() is the one device-to-host read."""
+
+    N_STATE = 16
+
+    def __init__(self, tree_dists=None, taxonomy=None, topk=5):
+        super().__init__()
+        if topk < 1:
+            raise ValueError(f"topk ({topk}) < 1")
+        self.topk = int(topk)
+        self.taxonomy = taxonomy
+        self.register_buffer("state", torch.zeros(self.N_STATE, dtype=torch.float64))
+        self.register_buffer("tree_dists", tree_dists, persistent=False)
+        paths = None
+        if taxonomy is not None:
+            paths = torch.from_numpy(np.ascontiguousarray(taxonomy.leaf_paths.astype(np.int32)))
+        self.register_buffer("leaf_paths", paths, persistent=False)
+        self.pred = self.rank = self.nll = self.dist = self.tier_hit = None  # the last batch's rows
+
+    @property
+    def has_dist(self):
+        return self.tree_dists is not None or self.leaf_paths is not None
+
+    def reset(self):
+        self.state.zero_()
+
+    @torch.no_grad()
+    def update(self, outputs, targets):
+        if isinstance(outputs, (list, tuple)):
+            outputs = outputs[-1]  # the finest tier's logits, as FineGrainedAccuracy scores
+        if targets.dtype.is_floating_point:
+            raise ValueError("EvalMetrics takes integer class targets")
+        if self.state.device != outputs.device:
+            self.to(outputs.device)
+        kw = {}
+        if self.leaf_paths is not None:  # path mode (also when a matrix was given as well)
+            if targets.ndim == 2 and targets.shape[1] == N_TIERS:
+                tp = targets.to(torch.int64).contiguous()
+                targets = tp
+            else:  # leaf ids: their paths, out-of-range ids (counted invalid by the kernel) clamped
+                leaf = targets[:, -1] if targets.ndim == 2 else targets
+                tp = self.leaf_paths[leaf.long().clamp(0, self.leaf_paths.shape[0] - 1)].to(torch.int64)
+            kw = dict(leaf_paths=self.leaf_paths, target_paths=tp, tier_hit=True)
+        elif self.tree_dists is not None:
+            kw = dict(tree_dists=self.tree_dists)
+        self.pred, self.rank, self.nll, self.dist, self.tier_hit = ops.eval_metrics(
+            outputs, targets, self.state, topk=self.topk, **kw)
+
+    def compute(self):
+        """{"acc@1", "acc@{topk}", "cross-entropy"[, "tree-dist"][, "acc@1/tier0" .. "tier6"]} as
+        Python floats over every update() since reset(), summed over the ranks when
+        torch.distributed is initialised."""
+        state = self.state
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            state = state.clone()
+            torch.distributed.all_reduce(state, op=torch.distributed.ReduceOp.SUM)
+        s = state.tolist()  # the one device-to-host read
+        if s[5] != 0:
+            raise ValueError(f"{int(s[5])} target(s) outside [0, num_classes) were passed to update()")
+        n = s[0]
+        div = (lambda x: x / n) if n else (lambda x: float("nan"))
+        out = {"acc@1": div(s[1]), f"acc@{self.topk}": div(s[2]), "cross-entropy": div(s[3])}
+        if self.has_dist:
+            out["tree-dist"] = div(s[4])
+        if self.leaf_paths is not None:
+            for t in range(N_TIERS):
+                out[f"acc@1/tier{t}"] = div(s[6 + t])
+        return out
+
+
 class LeafCountLookup:
     """Leaves under every node, for split tooling (hierarchy.py:333-368)."""
 

@@ -103,12 +103,29 @@ class DatasetInfo:
 class Model(torch.nn.Module):
     """ComposerModel surface (models.py:121-152)."""
 
-    def __init__(self, module, train_metrics, val_metrics, loss_fn):
+    def __init__(self, module, train_metrics, val_metrics, loss_fn, metrics_info=None):
         super().__init__()
         self.module = module
         self.loss_fn = loss_fn
         self.train_metrics = train_metrics
         self.val_metrics = val_metrics
+        # (hierarchy variant, config.is_train, DatasetInfo) from build_composer_model: what
+        # fused_metrics() needs to score what the dicts above score
+        self._metrics_info = metrics_info
+
+    def fused_metrics(self, is_train=False):
+        """A fresh hierarchy.EvalMetrics, on the parameters' device, reporting what
+        get_metrics(is_train) reports (models.py:61-101) from one kernel pass per batch:
+        acc@1, acc@5, cross-entropy, with tree-dist where the reference adds it (the validation
+        metrics of "multitask"; every set when the config is not a training one); the "hxe"
+        variant's taxonomy also gives tree-dist and the per-tier accuracies."""
+        variant, cfg_train, info = self._metrics_info or ("", True, None)
+        with_dist = (variant == "multitask" and not is_train) or not cfg_train
+        m = hierarchy.EvalMetrics(
+            tree_dists=info.tree_dists if info is not None and with_dist else None,
+            taxonomy=info.taxonomy if info is not None and variant == "hxe" else None, topk=5)
+        p = next(self.parameters(), None)
+        return m.to(p.device) if p is not None else m
 
     def loss(self, outputs, batch, *args, **kwargs):
         _, targets = batch
@@ -173,4 +190,5 @@ def build_composer_model(config, dataset_info: DatasetInfo, **model_kwargs):
         loss_fn = hierarchy.soft_cross_entropy
     else:
         raise ValueError(variant)
-    return Model(model, train_metrics=train_metrics, val_metrics=val_metrics, loss_fn=loss_fn)
+    return Model(model, train_metrics=train_metrics, val_metrics=val_metrics, loss_fn=loss_fn,
+                 metrics_info=(variant, bool(config.is_train), dataset_info))

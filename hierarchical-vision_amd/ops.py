@@ -1837,3 +1837,80 @@ def hierarchical_cross_entropy_soft(logits, soft, perm, rank_off, child_lo, chil
     loss, node_lse, node_t = HierarchicalSoftCE.apply(logits, _f32(soft.detach()), perm, rank_off,
                                                       child_lo, child_hi, anc, level_coeff)
     return (loss, node_lse, node_t) if return_nodes else loss
+
+
+# --------------------------------------------------------------------------- evaluation metrics
+def _dev_ptr(t, what):
+    """Device address of a tensor the kernel reads through explicit strides (a view is fine)."""
+    if not t.is_cuda:
+        raise RuntimeError(f"libhvk ops run on the GPU only; got a CPU tensor ({what})")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def eval_metrics(logits, targets, state, topk=5, tree_dists=None, leaf_paths=None, target_paths=None,
+                 tier_hit=False):
+    """hvk_eval_metrics (include/hvk.h): per-row argmax, target rank, NLL and tree distance of
+    `logits` [B, L] (f32 or bf16; any row stride, so a column slice or a padded buffer is read in
+    place) against the classes `targets` ([B], or [B, T] integer labels whose last column counts,
+    read through its stride), added into `state` (float64 [16] on the device).  Tree distance
+    from `tree_dists` (uint8 or f32 [L, L]) or from `leaf_paths` (int32 [L, 7]) with
+    `target_paths` (int64 [B, 7]); `tier_hit`: also the per-tier hit bits (leaf_paths only).
+    Not differentiable, no host synchronisation.  Returns (pred, rank, nll, dist, tier_hit or
+    None), [B] each."""
+    if not logits.is_cuda:
+        raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (logits)")
+    if logits.ndim != 2:
+        raise ValueError(f"logits must be [B, L], got {tuple(logits.shape)}")
+    logits = logits.detach()
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        logits = logits.float()
+    B, L = logits.shape
+    if B > 0 and L > 0 and logits.stride(1) != 1:
+        logits = logits.contiguous()
+    ld = logits.stride(0) if B > 1 else L
+    if ld < L:  # an expanded (stride 0) batch
+        logits = logits.contiguous()
+        ld = L
+    if targets.dtype.is_floating_point or targets.dtype == torch.bool:
+        raise ValueError("eval_metrics takes integer class targets")
+    if targets.ndim not in (1, 2) or targets.shape[0] != B:
+        raise ValueError(f"targets {tuple(targets.shape)} do not fit logits {tuple(logits.shape)}")
+    if targets.dtype != torch.int64:
+        targets = targets.to(torch.int64)
+    if targets.ndim == 2:
+        if targets.shape[1] < 1:
+            raise ValueError("targets [B, 0]")
+        if targets.stride(1) != 1 or (B > 1 and targets.stride(0) < targets.shape[1]):
+            targets = targets.contiguous()
+        t_stride = targets.stride(0) if B > 1 else targets.shape[1]
+        t_off = targets.shape[1] - 1
+    else:
+        if B > 1 and targets.stride(0) < 1:
+            targets = targets.contiguous()
+        t_stride, t_off = (targets.stride(0) if B > 1 else 1), 0
+    dev = logits.device
+    if state.dtype != torch.float64 or state.numel() != 16 or not state.is_contiguous():
+        raise ValueError("state must be a contiguous float64 tensor of 16 elements")
+    dist_dtype = 0
+    if tree_dists is not None:
+        if tree_dists.dtype not in (torch.uint8, torch.float32) or tuple(tree_dists.shape) != (L, L):
+            raise ValueError(f"tree_dists must be uint8 or float32 [{L}, {L}], got {tree_dists.dtype} "
+                             f"{tuple(tree_dists.shape)}")
+        dist_dtype = 1 if tree_dists.dtype == torch.float32 else 0
+    if leaf_paths is not None:
+        if leaf_paths.dtype != torch.int32 or tuple(leaf_paths.shape) != (L, 7):
+            raise ValueError(f"leaf_paths must be int32 [{L}, 7]")
+        if target_paths is not None and (target_paths.dtype != torch.int64
+                                         or tuple(target_paths.shape) != (B, 7)):
+            raise ValueError(f"target_paths must be int64 [{B}, 7]")
+    pred = torch.empty(B, device=dev, dtype=torch.int32)
+    rank = torch.empty(B, device=dev, dtype=torch.int32)
+    nll = torch.empty(B, device=dev, dtype=torch.float32)
+    dist = torch.empty(B, device=dev, dtype=torch.int32)
+    hit = torch.empty(B, device=dev, dtype=torch.uint8) if tier_hit else None
+    if B == 0:  # nothing to add (an empty tensor has no address to pass)
+        return pred, rank, nll, dist, hit
+    call("hvk_eval_metrics", _dev_ptr(logits, "logits"), 1 if logits.dtype == torch.bfloat16 else 0, B, L, ld,
+         _dev_ptr(targets, "targets"), t_stride, t_off, ptr(tree_dists), dist_dtype, ptr(leaf_paths),
+         ptr(target_paths), int(topk), ptr(pred), ptr(rank), ptr(nll), ptr(dist), ptr(hit), ptr(state), stream())
+    return pred, rank, nll, dist, hit

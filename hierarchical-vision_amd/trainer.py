@@ -10,7 +10,11 @@ is captured once as a HIP graph (torch.cuda.CUDAGraph over hipGraph), the gradie
 clipping + optimizer update as a second one; a step is two graph replays with, for
 world > 1, the bucketed RCCL all-reduce issued eagerly between them (RCCL is not captured).
 The batch must live in the static tensors passed to capture() (copy new data into them).
-BATCH_END algorithms (EMA: host-side counters) run eagerly after the replays."""
+BATCH_END algorithms (EMA: host-side counters) run eagerly after the replays.
+
+Evaluation (`eval()`): EVAL_START -> per batch a no-grad forward, the metrics update (one fused
+kernel pass, hierarchy.EvalMetrics) and EVAL_BATCH_END -> EVAL_END; EMA lends the model its
+averaged weights for the duration."""
 import time
 
 import torch
@@ -112,6 +116,9 @@ class Trainer:
         # (profiles/round6/inflight/).
         self.max_steps_in_flight = None
         self._in_flight = []
+        # a hierarchy.EvalMetrics -> every training forward also updates it with the step's
+        # outputs and its original targets (one more launch pair, capturable); None: off
+        self.train_metrics = None
         self._run(Event.INIT)
 
     def _run(self, event):
@@ -142,6 +149,7 @@ class Trainer:
             ops.reset_leaf_uses()  # the side stream's per-parameter use counts start with this forward
             with torch.autocast(device_type=dev_type, dtype=self.dtype, enabled=dev_type == "cuda"):
                 st.outputs = self.model(st.batch)
+            self._update_train_metrics()
             self._run(Event.BEFORE_LOSS)
             st.loss = self.model.loss(st.outputs, st.batch)
             self._run(Event.AFTER_LOSS)
@@ -182,6 +190,58 @@ class Trainer:
             self._in_flight.append(done)
         return st.loss
 
+    def _update_train_metrics(self):
+        """Right after the forward, before BEFORE_LOSS swaps the targets (LabelSmoothing)."""
+        if self.train_metrics is not None:
+            outs = self.state.outputs
+            outs = [o.detach() for o in outs] if isinstance(outs, (list, tuple)) else outs.detach()
+            self.train_metrics.update(outs, self.state.batch[1])
+
+    # ---------------------------------------------------------------- evaluation
+    def eval(self, batches, metrics=None):
+        """One evaluation pass (composer's trainer.eval(), main.py:104-131) over an iterable of
+        (inputs, targets) batches, the last of which may be smaller: EVAL_START (EMA exchanges
+        the averaged weights in), then per batch the device transforms, a no-grad forward under
+        the trainer's autocast, metrics.update(outputs, targets) and EVAL_BATCH_END; EVAL_END
+        (the weights exchanged back) also when a batch raises.  Returns metrics.compute().
+
+        `metrics`: a hierarchy.EvalMetrics (default: model.fused_metrics()), or a dict of metric
+        objects such as model.get_metrics(), each updated per batch and returned as
+        {name: metric.compute()} -- the only form for a CPU model.  As in composer, the metrics
+        are reset() when the pass starts.  The training state
+        (.grad, gradient buckets, timestamp_batch, the model's train / eval flag) is untouched."""
+        st = self.state
+        if metrics is None:
+            if not hasattr(self.model, "fused_metrics"):
+                raise ValueError("the model has no fused_metrics(): pass `metrics`")
+            metrics = self.model.fused_metrics()
+        many = isinstance(metrics, dict)
+        for m in (metrics.values() if many else (metrics,)):
+            m.reset()
+        was_training = self.model.training
+        saved = st.batch, st.outputs
+        try:
+            self._run(Event.EVAL_START)
+            self.model.eval()
+            with torch.no_grad():
+                for batch in batches:
+                    if self.device_transforms is not None:
+                        batch = self.device_transforms(batch)
+                    dev_type = batch[0].device.type
+                    st.batch = batch
+                    with torch.autocast(device_type=dev_type, dtype=self.dtype, enabled=dev_type == "cuda"):
+                        st.outputs = self.model(batch)
+                    for m in (metrics.values() if many else (metrics,)):
+                        m.update(st.outputs, batch[1])
+                    self._run(Event.EVAL_BATCH_END)
+        finally:
+            st.batch, st.outputs = saved
+            self.model.train(was_training)
+            self._run(Event.EVAL_END)
+        if many:
+            return {k: m.compute() for k, m in metrics.items()}
+        return metrics.compute()
+
     def _grad_mean(self, wait=True):
         """Bucket all-reduces done -> mean gradients: handed to the optimizer as a scale when it
         can fold it into its update (no extra pass), else divided in place."""
@@ -204,6 +264,7 @@ class Trainer:
             self.buckets.zero_()
         with torch.autocast(device_type="cuda", dtype=self.dtype):
             st.outputs = self.model(st.batch)
+        self._update_train_metrics()
         self._run(Event.BEFORE_LOSS)
         st.loss = self.model.loss(st.outputs, st.batch)
         self._run(Event.AFTER_LOSS)
@@ -228,12 +289,19 @@ class Trainer:
         torch.cuda.synchronize()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
+        # the warm-up steps are real steps, but their batch is not new data for the train metrics
+        tm = self.train_metrics
+        tm_state = tm.state.clone() if tm is not None else None
         with torch.cuda.stream(side):
             for _ in range(warmup):
                 self.train_step(batch)
         torch.cuda.current_stream().wait_stream(side)
         self.state.outputs = self.state.loss = None
         torch.cuda.synchronize()
+        if tm is not None:
+            if tm.state.device != tm_state.device:  # the first update moved it to the GPU
+                tm_state = tm_state.to(tm.state.device)
+            tm.state.copy_(tm_state)
         self.buckets.defer = True
         # gradients allocated inside the graph's pool, kept across replays (with buckets the
         # hooks copy them into the bucket views and leave .grad = view)

@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 16
+#define HVK_ABI_VERSION 17
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -526,6 +526,38 @@ int hvk_hxe_soft_fwd(const float* logits, const float* soft, int B, int L, const
 int hvk_hxe_soft_bwd(const float* logits, const float* soft, int B, int L, const int* perm,
                      int n_nodes, const int* anc, const float* level_coeff, const float* node_lse,
                      const float* node_t, const float* grad_out, float* dlogits, void* stream);
+
+/* ---- Evaluation metrics (hierarchy.py:97-180, models.py:61-101) -------------------
+ * acc@1, acc@topk, cross-entropy and tree distance of a batch from one read of each logit row,
+ * added into a persistent device state.  Not differentiable.
+ * logits: f32 (logits_dtype 0) or bf16 (1), [B, L] with row stride ld >= L elements; rows that
+ * start on a 16-B boundary are read with 16-B loads, others element by element.  The class of
+ * sample b is targets[b * t_stride + t_off] (t_stride 7, t_off 6: the leaf column of [B, 7] tier
+ * labels, no copy).  Tree distance, one of: tree_dists, uint8 (dist_dtype 0) or f32 (1) [L, L],
+ * read at [pred, target]; or leaf_paths int [L, 7] (tier ids of every leaf) with target_paths
+ * int64 [B, 7], which gives the same number without the L * L matrix; or neither.
+ * Per row, into [B] buffers:
+ *   pred  argmax; equal values compare as floats (-0.0 == +0.0) and the LOWEST index wins
+ *   rank  #{j : z_j > z_t, or z_j == z_t and j < t}: the target's position in a stable
+ *         descending sort, so the sample counts for acc@k iff rank < k
+ *   nll   LSE(z) - z_t, max-shifted, f32 accumulation, IEEE expf / logf
+ *   dist  tree_dists[pred, t]; or the smallest lvl in 0..6 with leaf_paths[pred, 6 - lvl] ==
+ *         target_paths[b, 6 - lvl], 7 if none; or -1
+ *   tier_hit (optional, only with leaf_paths)  bit q set iff leaf_paths[pred, q] == target_paths[b, q]
+ * A target outside [0, L) is never dereferenced: rank -1, nll NaN, dist -1, tier_hit 0, and the
+ * row is counted as invalid only.  -inf logits are ordinary values; NaN logits never fault (pred
+ * stays in [0, L); nll is NaN as torch's is).
+ * state: double [16], added to: [0] valid rows, [1] rows with rank < 1, [2] rows with rank <
+ * min(topk, L), [3] sum nll, [4] sum dist, [5] invalid rows, [6..12] hits of tier 0..6, rest
+ * reserved.  The summation order depends on B only and nothing is atomic: equal inputs leave
+ * bit-identical state.  Two launches on `stream`, no synchronisation or allocation (capturable).
+ * B == 0 returns HVK_OK without a launch. */
+int hvk_eval_metrics(const void* logits, int logits_dtype /* 0 f32, 1 bf16 */, int B, int L, int ld,
+                     const int64_t* targets, int t_stride, int t_off,
+                     const void* tree_dists, int dist_dtype /* 0 u8, 1 f32 */,
+                     const int* leaf_paths, const int64_t* target_paths,
+                     int topk, int* pred, int* rank, float* nll, int* dist, unsigned char* tier_hit,
+                     double* state, void* stream);
 
 #ifdef __cplusplus
 }
