@@ -7,6 +7,7 @@ Modules mirror the reference files they replace:
   models.py      <- models.py      (build_model / build_composer_model / Model)
   algorithmic.py <- algorithmic.py (LabelSmoothing for list outputs)
   configs.py     <- configs.py     (structured config schema)
+  simpleshot.py  <- simpleshot.py  (nearest-centroid evaluation of frozen features, flat / hierarchical)
   ddp.py            RCCL gradient all-reduce, bucketed, overlapped with backward
   ops.py            autograd Functions over the C ABI of libhvk.so
   _lib.py           ctypes binding of libhvk.so (include/hvk.h)

@@ -121,10 +121,16 @@ SIGNATURES = {
     "hvk_hxe_soft_fwd": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "hvk_hxe_soft_bwd": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
     "hvk_eval_metrics": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "hvk_ss_prepare": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "hvk_ss_accumulate": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p]),
+    "hvk_ss_finalize": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "hvk_ss_predict_flat_workspace": (_sz, [_i, _i]),
+    "hvk_ss_predict_flat": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _sz, _p]),
+    "hvk_ss_predict_tree": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
 }
 
 _lib = None
-ABI_VERSION = 17  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
+ABI_VERSION = 18  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
 
 
 def load():

@@ -578,3 +578,13 @@ class LeafCountLookup:
         if best is None:
             raise RuntimeError("no values in lookup!")
         return best
+
+
+def __getattr__(name):
+    """HierarchicalNearestCentroid lives where the reference keeps it (hierarchy.py:488-597); it is
+    defined in simpleshot.py and resolved on first use, so neither module imports the other at
+    load time."""
+    if name == "HierarchicalNearestCentroid":
+        from .simpleshot import HierarchicalNearestCentroid
+        return HierarchicalNearestCentroid
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

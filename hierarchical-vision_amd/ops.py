@@ -1914,3 +1914,161 @@ def eval_metrics(logits, targets, state, topk=5, tree_dists=None, leaf_paths=Non
          _dev_ptr(targets, "targets"), t_stride, t_off, ptr(tree_dists), dist_dtype, ptr(leaf_paths),
          ptr(target_paths), int(topk), ptr(pred), ptr(rank), ptr(nll), ptr(dist), ptr(hit), ptr(state), stream())
     return pred, rank, nll, dist, hit
+
+
+# --------------------------------------------------------------------------- SimpleShot
+_SS_WORKSPACE = {}  # device -> uint8 buffer of hvk_ss_predict_flat's partial (min, index) pairs
+
+
+def _ss_features(x, what="features"):
+    """x as the dense f32 [B, D] the fit / predict kernels read (prepared features already are)."""
+    if not x.is_cuda:
+        raise RuntimeError(f"libhvk ops run on the GPU only; got a CPU tensor ({what})")
+    if x.ndim != 2:
+        raise ValueError(f"{what} must be [B, D], got {tuple(x.shape)}")
+    x = x.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def ss_prepare(features, centered=False, l2_normalized=False):
+    """hvk_ss_prepare (include/hvk.h): `features` [B, D] (f32 or bf16, any row stride) -> dense f32
+    [B, D], divided by the row mean (`centered`, simpleshot.py:148-154) and / or then by the row's
+    L2 norm (`l2_normalized`, simpleshot.py:139-145).  With neither flag it is the f32 copy."""
+    if not features.is_cuda:
+        raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (features)")
+    if features.ndim != 2:
+        raise ValueError(f"features must be [B, D], got {tuple(features.shape)}")
+    x = features.detach()
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    B, D = x.shape
+    if B > 0 and D > 0 and x.stride(1) != 1:
+        x = x.contiguous()
+    ld = x.stride(0) if B > 1 else D
+    if ld < D:  # an expanded (stride 0) batch
+        x = x.contiguous()
+        ld = D
+    out = torch.empty(B, D, device=x.device, dtype=torch.float32)
+    if B == 0 or D == 0:
+        return out
+    call("hvk_ss_prepare", _dev_ptr(x, "features"), 1 if x.dtype == torch.bfloat16 else 0, B, D, ld,
+         int(bool(centered)), int(bool(l2_normalized)), ptr(out), stream())
+    return out
+
+
+def ss_accumulate(x, labels, sums, counts, state):
+    """hvk_ss_accumulate: add the rows of `x` (f32 [B, D]) to the float64 `sums` [L, D] and int64
+    `counts` [L] of their classes -- `labels` [B], or the last column of [B, T] integer labels,
+    read through its stride -- in ascending row order per class (bit-identical for any split into
+    consecutive batches).  Labels outside [0, L) are skipped and counted in `state` (float64 [4]:
+    rows added, rows skipped)."""
+    x = _ss_features(x)
+    B, D = x.shape
+    if not labels.is_cuda:
+        raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (labels)")
+    if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise ValueError("ss_accumulate takes integer class labels")
+    if labels.ndim not in (1, 2) or labels.shape[0] != B or (labels.ndim == 2 and labels.shape[1] < 1):
+        raise ValueError(f"labels {tuple(labels.shape)} do not fit features {tuple(x.shape)}")
+    if labels.dtype != torch.int64:
+        labels = labels.to(torch.int64)
+    if labels.ndim == 2:
+        if labels.stride(1) != 1 or (B > 1 and labels.stride(0) < labels.shape[1]):
+            labels = labels.contiguous()
+        t_stride = labels.stride(0) if B > 1 else labels.shape[1]
+        t_off = labels.shape[1] - 1
+        col = labels[:, -1]
+    else:
+        if B > 1 and labels.stride(0) < 1:
+            labels = labels.contiguous()
+        t_stride, t_off, col = (labels.stride(0) if B > 1 else 1), 0, labels
+    if (sums.dtype != torch.float64 or sums.ndim != 2 or sums.shape[1] != D or not sums.is_contiguous()
+            or counts.dtype != torch.int64 or counts.shape != (sums.shape[0],) or not counts.is_contiguous()):
+        raise ValueError(f"sums must be contiguous float64 [L, {D}] and counts int64 [L]")
+    if state.dtype != torch.float64 or state.numel() != 4 or not state.is_contiguous():
+        raise ValueError("state must be a contiguous float64 tensor of 4 elements")
+    if B == 0:
+        return
+    order = torch.argsort(col, stable=True)
+    call("hvk_ss_accumulate", ptr(x), B, D, _dev_ptr(labels, "labels"), t_stride, t_off, ptr(order),
+         sums.shape[0], ptr(sums), ptr(counts), ptr(state), stream())
+
+
+def _ss_tier_base(tier_base):
+    return (ctypes.c_int * len(tier_base))(*[int(v) for v in tier_base])
+
+
+def ss_finalize(sums, counts, tier_base, child_ptr, child_idx):
+    """hvk_ss_finalize: `sums` float64 [n_nodes, D] / `counts` int64 [n_nodes] with the leaf tier
+    filled; the tiers above are overwritten bottom-up through the CSR children lists (`tier_base`:
+    a host sequence of n_tiers + 1 ints; `child_ptr`, `child_idx`: int32 device tensors, None with
+    one tier).  Returns (centroids f32 [n_nodes, D], cnorm f32 [n_nodes])."""
+    if not sums.is_cuda:
+        raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (sums)")
+    n_nodes, D = sums.shape
+    n_tiers = len(tier_base) - 1
+    if (sums.dtype != torch.float64 or counts.dtype != torch.int64 or counts.shape != (n_nodes,)
+            or int(tier_base[-1]) != n_nodes):
+        raise ValueError("sums float64 [n_nodes, D], counts int64 [n_nodes], tier_base[-1] == n_nodes")
+    _ss_check_csr(tier_base, child_ptr, child_idx)
+    cent = torch.empty(n_nodes, D, device=sums.device, dtype=torch.float32)
+    cnorm = torch.empty(n_nodes, device=sums.device, dtype=torch.float32)
+    call("hvk_ss_finalize", ptr(sums), ptr(counts), D, n_tiers, _ss_tier_base(tier_base), ptr(child_ptr),
+         ptr(child_idx), ptr(cent), ptr(cnorm), stream())
+    return cent, cnorm
+
+
+def _ss_check_csr(tier_base, child_ptr, child_idx):
+    n_tiers = len(tier_base) - 1
+    if n_tiers == 1:
+        return
+    if (child_ptr is None or child_idx is None or child_ptr.dtype != torch.int32 or child_idx.dtype != torch.int32
+            or child_ptr.numel() != int(tier_base[-2]) + 1
+            or child_idx.numel() != int(tier_base[-1]) - int(tier_base[1])):
+        raise ValueError("child_ptr must be int32 [internal nodes + 1] and child_idx int32 [nodes below tier 0]")
+
+
+def ss_predict_flat(x, centroids, cnorm):
+    """hvk_ss_predict_flat: argmin_c (cnorm[c] - 2 x . c) of every row of `x` ([B, D], D % 4 == 0)
+    over `centroids` f32 [L, D] on the f32 MFMA; int32 [B].  The lowest index wins ties and a
+    class with cnorm = +inf is never chosen."""
+    x = _ss_features(x)
+    B, D = x.shape
+    if not centroids.is_cuda or not cnorm.is_cuda:
+        raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (centroids)")
+    L = centroids.shape[0]
+    if (centroids.dtype != torch.float32 or centroids.ndim != 2 or centroids.shape[1] != D
+            or cnorm.dtype != torch.float32 or cnorm.shape != (L,)):
+        raise ValueError(f"centroids must be float32 [L, {D}] and cnorm float32 [L]")
+    pred = torch.empty(B, device=x.device, dtype=torch.int32)
+    if B == 0:
+        return pred
+    need = _lib.load().hvk_ss_predict_flat_workspace(B, L)
+    ws = _SS_WORKSPACE.get(x.device)
+    if ws is None or ws.numel() < need:
+        ws = _SS_WORKSPACE[x.device] = torch.empty(max(need, 1 << 20), device=x.device, dtype=torch.uint8)
+    call("hvk_ss_predict_flat", ptr(x), B, D, ptr(centroids), ptr(cnorm), L, ptr(pred), ptr(ws), ws.numel(),
+         stream())
+    return pred
+
+
+def ss_predict_tree(x, centroids, counts, tier_base, child_ptr, child_idx):
+    """hvk_ss_predict_tree: the top-down path of every row of `x` ([B, D]) through the tree whose
+    nodes have `centroids` f32 [n_nodes, D] and `counts` int64 [n_nodes]; int32 [B, n_tiers]."""
+    x = _ss_features(x)
+    B, D = x.shape
+    if not centroids.is_cuda or not counts.is_cuda:
+        raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (centroids)")
+    n_nodes, n_tiers = int(tier_base[-1]), len(tier_base) - 1
+    if (centroids.dtype != torch.float32 or tuple(centroids.shape) != (n_nodes, D)
+            or counts.dtype != torch.int64 or counts.shape != (n_nodes,)):
+        raise ValueError(f"centroids must be float32 [{n_nodes}, {D}] and counts int64 [{n_nodes}]")
+    _ss_check_csr(tier_base, child_ptr, child_idx)
+    pred = torch.empty(B, n_tiers, device=x.device, dtype=torch.int32)
+    if B == 0:
+        return pred
+    call("hvk_ss_predict_tree", ptr(x), B, D, ptr(centroids), ptr(counts), n_tiers, _ss_tier_base(tier_base),
+         ptr(child_ptr), ptr(child_idx), ptr(pred), stream())
+    return pred

@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 17
+#define HVK_ABI_VERSION 18
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -558,6 +558,72 @@ int hvk_eval_metrics(const void* logits, int logits_dtype /* 0 f32, 1 bf16 */, i
                      const int* leaf_paths, const int64_t* target_paths,
                      int topk, int* pred, int* rank, float* nll, int* dist, unsigned char* tier_hit,
                      double* state, void* stream);
+
+/* ---- SimpleShot evaluation (simpleshot.py:139-203, hierarchy.py:488-597) ----------------
+ * Nearest-centroid classification of frozen features, flat or top-down through the taxonomy.
+ * Nodes are numbered tier by tier: node i of tier t is row tier_base[t] + i of every [n_nodes, .]
+ * buffer; tier_base is a HOST array of n_tiers + 1 ints (1 <= n_tiers <= 8), tier_base[0] = 0,
+ * strictly growing, tier_base[n_tiers] = n_nodes.  The last tier holds the L leaf classes; one
+ * tier is the flat classifier.  The tree is CSR children lists on the device: the children of node
+ * i of tier t < n_tiers - 1 are the tier-(t + 1) ids child_idx[child_ptr[tier_base[t] + i] ..
+ * child_ptr[tier_base[t] + i + 1]), ascending (child_ptr int [tier_base[n_tiers - 1] + 1],
+ * child_idx int [n_nodes - tier_base[1]]; both may be NULL with one tier).  An id outside its tier
+ * is skipped, never dereferenced.  Nothing is atomic: equal inputs give bit-identical outputs.
+ * Every entry point validates before its first launch; B == 0 returns HVK_OK without a launch.
+ *
+ * hvk_ss_prepare: features x, f32 (x_dtype 0) or bf16 (1), [B, D] with row stride ld >= D
+ * elements -> out f32 [B, D] dense.  centered: x / mean_k(x_k) per row (simpleshot.py:148-154:
+ * a division by the row's own mean, not the paper's subtraction of the training mean);
+ * l2_normalized: then x / ||x||_2.  f32 throughout with IEEE divisions and square root; each row
+ * sum is 64 per-lane partial sums folded by a fixed butterfly.  A zero mean or norm gives inf /
+ * NaN as numpy does.  One launch. */
+int hvk_ss_prepare(const void* x, int x_dtype /* 0 f32, 1 bf16 */, int B, int D, int ld, int centered,
+                   int l2_normalized, float* out, void* stream);
+
+/* hvk_ss_accumulate: the fit, once per batch.  Adds the rows of x (f32 [B, D] dense, prepared)
+ * into the leaf tier's slice of the running sums (sums: double [L, D]) and counts (int64 [L]).
+ * The class of row b is labels[b * t_stride + t_off] (t_stride 7, t_off 6: the leaf column of
+ * [B, 7] tier labels, no copy); order: int64 [B], a STABLE argsort of that column.  Each class
+ * has one writer, which adds its rows to the running sum one at a time in ascending row index:
+ * N rows in one call or in any split into consecutive batches leave bit-identical sums.  A label
+ * outside [0, L) is never dereferenced: the row is skipped.  state: double [4], added to:
+ * [0] rows added, [1] rows skipped (invalid), rest reserved.  One launch. */
+int hvk_ss_accumulate(const float* x, int B, int D, const int64_t* labels, int t_stride, int t_off,
+                      const int64_t* order, int L, double* sums, long long* counts, double* state,
+                      void* stream);
+
+/* hvk_ss_finalize: centroids of every node.  sums double [n_nodes, D] and counts int64 [n_nodes]
+ * hold the leaf tier (from hvk_ss_accumulate); the rows of the tiers above are OVERWRITTEN
+ * bottom-up, a node's sum and count being the sums over its children in ascending child id (so
+ * the call may be repeated after further batches).  Outputs: centroids f32 [n_nodes, D], the
+ * float64 mean sum / count rounded once (a zero row where count is 0); cnorm f32 [n_nodes], the
+ * squared norm of the f32 centroid, +inf where count is 0.  n_tiers launches. */
+int hvk_ss_finalize(double* sums, long long* counts, int D, int n_tiers, const int* tier_base,
+                    const int* child_ptr, const int* child_idx, float* centroids, float* cnorm,
+                    void* stream);
+
+/* hvk_ss_predict_flat: pred[b] = argmin_c (cnorm[c] - 2 x_b . c_c) over the L rows of centroids
+ * (f32 [L, D], e.g. the leaf tier's slice), x f32 [B, D] dense; both 16-byte aligned, D % 4 == 0.
+ * The products run on the f32-input MFMA (v_mfma_f32_16x16x4_f32: exact f32 operands, f32
+ * accumulation); the [B, L] scores exist in registers only.  The class range is split over
+ * workgroups, whose partial (min, index) pairs go through `workspace`
+ * (hvk_ss_predict_flat_workspace(B, L) bytes) to a second small kernel.  Equal scores: the lowest
+ * class index wins; a class with cnorm = +inf is never chosen; NaN features never fault and pred
+ * stays in [0, L) (0 when nothing compared).  pred: int [B].  Two launches. */
+size_t hvk_ss_predict_flat_workspace(int B, int L);
+int hvk_ss_predict_flat(const float* x, int B, int D, const float* centroids, const float* cnorm, int L,
+                        int* pred, void* workspace, size_t workspace_bytes, void* stream);
+
+/* hvk_ss_predict_tree: the top-down prediction (hierarchy.py:538-597).  One wave per sample keeps
+ * the row of x (f32 [B, D] dense, D <= 4096) in LDS and walks the tree once: the candidates are
+ * every tier-0 node, then the children of the node chosen one tier up; each candidate is scored
+ * by sum_k (x_k - c_k)^2 in f32 over centroids f32 [n_nodes, D].  Candidates with counts (int64
+ * [n_nodes], as finalized) == 0 are skipped, the lowest id wins among equal distances, and a node
+ * whose children are all empty passes its first child on, so pred -- int [B, n_tiers], tier ids
+ * -- is always a path of the tree.  One launch. */
+int hvk_ss_predict_tree(const float* x, int B, int D, const float* centroids, const long long* counts,
+                        int n_tiers, const int* tier_base, const int* child_ptr, const int* child_idx,
+                        int* pred, void* stream);
 
 #ifdef __cplusplus
 }
