@@ -10,7 +10,7 @@ import ctypes
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, routes
 from ._lib import call, ptr, stream
 from .options import OPTIONS
 
@@ -76,6 +76,21 @@ def _bf16(t):
 def _f32(t):
     t = t if t.dtype == torch.float32 else t.float()
     return t.contiguous()
+
+
+_WORKSPACES = {}
+
+
+def _workspace(tag, device, nbytes, zero=False):
+    """The persistent f32 workspace of the op `tag`, one per device and size (no allocation or
+    memset per call).  The tag is part of the key: a `zero` workspace is zero-filled once and its
+    kernels leave it zero again (W-MSA backward, include/hvk.h), so no other op may be handed it."""
+    key = (tag, device, nbytes)
+    ws = _WORKSPACES.get(key)
+    if ws is None:
+        alloc = torch.zeros if zero else torch.empty
+        ws = _WORKSPACES[key] = alloc(nbytes // 4, device=device, dtype=torch.float32)
+    return ws
 
 
 # --------------------------------------------------------------------------- bf16 weights
@@ -161,13 +176,8 @@ def _split_k_chunks(rows):
 
 
 def _gelu_recompute(M, K, N1, N2):
-    """With options.gelu_recompute, MlpFn keeps only h = fc1(x) and recomputes GELU(h) inside
-    fc2's forward and weight gradient where both kernels are built (stage 0: K 96, N1 384,
-    N2 96).  Bit-identical results; off by default: on MI355X the recompute costs fc2 +80 µs
-    and its weight gradient +217 µs against the 233 µs the y write saves."""
-    lib = _lib.load()
-    return (OPTIONS.gelu_recompute and _linear_native(M, K, N1) and lib.hvk_linear_gelu_in_supported(M, N1, N2)
-            and lib.hvk_weight_grad_gelu_x_supported(M, N2, N1))
+    """MlpFn keeps only h = fc1(x) and recomputes GELU(h) where consumed (routes.mlp)."""
+    return routes.mlp(M, K, N1, N2) == "recompute"
 
 
 class _WgradStream:
@@ -193,7 +203,7 @@ def note_leaf_uses(leaves, ctx):
     """Count a forward use of each parameter in `leaves` (called by every Function's forward that
     takes parameters; ctx: its context).  A parameter used twice in one graph (tied weights, a
     module called twice) gets two gradients that autograd adds on the current stream, reading
-    side-written data without a wait: _wgrad_fork refuses it.  Forwards that build no graph (under
+    side-written data without a wait: _wgrad_side refuses it.  Forwards that build no graph (under
     no_grad: grad mode is off inside every Function.forward, and needs_input_grad follows
     requires_grad only) count as well, which errs on the safe side: until the next reset
     (Trainer, each microbatch) or scope exit such a parameter stays on the current stream."""
@@ -245,29 +255,6 @@ def _side_safe(t):
             and not t._backward_hooks and _WgradStream.uses.get(id(t), 0) == 1)
 
 
-def _wgrad_fork(leaves):
-    """(main, side) when the gradients of `leaves` (the parameters the launch produces gradients
-    for) may be computed on the side stream, else None."""
-    if not (OPTIONS.wgrad_stream and _WgradStream.active and leaves) or torch.cuda.is_current_stream_capturing():
-        return None
-    if not all(t is None or _side_safe(t) for t in leaves):
-        return None
-    if _WgradStream.side is None:
-        _WgradStream.side = torch.cuda.Stream()
-    main = torch.cuda.current_stream()
-    _WgradStream.side.wait_stream(main)
-    _WgradStream.forks += 1
-    return main, _WgradStream.side
-
-
-def _wgrad_outputs(*ts):
-    """Mark gradients a side-stream launch wrote (wgrad_produced_on_side), by storage address:
-    AccumulateGrad stores a detached alias (a new tensor object over the same storage)."""
-    for t in ts:
-        if t is not None:
-            _WgradStream.produced.add(t.untyped_storage().data_ptr())
-
-
 def wgrad_produced_on_side(t):
     """True for a gradient a side-stream launch wrote (since the last join): a consumer on the
     side stream needs no wait for the current stream to read it."""
@@ -290,18 +277,34 @@ def wgrad_hold(*tensors):
             t.record_stream(side)
 
 
-def _wgrad_joined(tensors, outputs=()):
-    """After launches on the side stream that read / write `tensors` (operands and workspaces,
-    allocated on the main stream) and write `outputs` (the gradients handed back to autograd): keep
-    the operands alive until the join (wgrad_hold), protect the outputs' memory with record_stream
-    (they are small; holding a reference would stop AccumulateGrad from stealing them -- it would
-    clone them on the current stream, racing the side stream), and make sure the main stream waits
-    for the side stream before the backward returns (an autograd final callback; outside a
-    backward, at once)."""
-    wgrad_hold(*tensors)
+@contextlib.contextmanager
+def _wgrad_side(leaves, operands, outputs):
+    """Run the body's launches on the weight-gradient side stream (yielded; it is torch's current
+    stream inside, made to wait for the one current before) where `leaves`, the parameters the
+    launches produce gradients for, allow it (_side_safe), else on the current stream (None
+    yielded).  After side-stream launches: `operands` (inputs and workspaces, allocated on the main
+    stream; a list may still grow inside the body) are kept alive until the join (wgrad_hold);
+    `outputs` (the gradients handed back to autograd) are marked as side-written by storage address
+    (wgrad_produced_on_side: AccumulateGrad stores a detached alias, a new tensor object over the
+    same storage) and protected with record_stream (they are small; holding a reference would stop
+    AccumulateGrad from stealing them -- it would clone them on the current stream, racing the side
+    stream); only then is the main stream made to wait for the side stream before the backward
+    returns (an autograd final callback; outside a backward at once, which forgets the marks)."""
+    if (not (OPTIONS.wgrad_stream and _WgradStream.active and leaves) or torch.cuda.is_current_stream_capturing()
+            or not all(t is None or _side_safe(t) for t in leaves)):
+        yield None
+        return
+    if _WgradStream.side is None:
+        _WgradStream.side = torch.cuda.Stream()
     side = _WgradStream.side
+    side.wait_stream(torch.cuda.current_stream())
+    _WgradStream.forks += 1
+    with torch.cuda.stream(side):
+        yield side
+    wgrad_hold(*operands)
     for t in outputs:
         if t is not None:
+            _WgradStream.produced.add(t.untyped_storage().data_ptr())
             t.record_stream(side)
     _WgradStream.pending = True
     if not _WgradStream.armed:
@@ -332,15 +335,7 @@ def wgrad_side_pending():
     return _WgradStream.side if _WgradStream.pending else None
 
 
-_DW_TOK = 32  # tokens per stage of libhvk's weight-gradient kernel (csrc/gemm_tn.hip TOK)
-
-
-def _dw_native(M, N, K, gelu_x=False):
-    """libhvk's weight-gradient kernel takes the shape: directly when 32 | M, else as a main launch
-    over the first M - M % 32 tokens plus one over the zero-padded 32-token tail (_dw_launch)."""
-    lib = _lib.load()
-    ok = lib.hvk_weight_grad_gelu_x_supported if gelu_x else lib.hvk_weight_grad_supported
-    return M > 0 and bool(ok(M - M % _DW_TOK if M >= _DW_TOK else _DW_TOK, N, K))
+_DW_TOK = routes.DW_TOK
 
 
 def _dw_launch(g, x, with_db, gelu_x, xs, keep):
@@ -385,36 +380,24 @@ def _dw_launch(g, x, with_db, gelu_x, xs, keep):
 
 
 def weight_grad(g, x, with_db=False, gelu_x=False, xshift=None, leaves=()):
-    """weight_grad_sync, on the weight-gradient side stream when `leaves` (the parameters whose
-    gradients dW / db are) allow it (wgrad_stream_scope) and libhvk's kernel is built for the
-    shape, else on the current stream."""
-    M, N = g.shape
-    K = x.shape[1]
-    fork = _wgrad_fork(leaves) if g.is_cuda and _dw_native(M, N, K, gelu_x) else None
-    if fork is None:
-        return weight_grad_sync(g, x, with_db, gelu_x, xshift)
-    main, side = fork
-    xs = _f32(xshift) if xshift is not None else None
-    keep = [xs]
-    with torch.cuda.stream(side):
-        dw, db = _dw_launch(g, x, with_db, gelu_x, xs, keep)
-    _wgrad_joined(keep, (dw, db))
-    _wgrad_outputs(dw, db)
-    return dw, db
-
-
-def weight_grad_sync(g, x, with_db=False, gelu_x=False, xshift=None):
     """(dW, db) = (g^T x, g.sum(0)) in f32 for g [M, N], x [M, K] bf16 with M = tokens (up to
     ~10^6): libhvk's token-chunked MFMA kernel with the bias gradient fused (hvk_weight_grad,
-    one pass over g) for every SwinV2 shape it is built for, any M (_dw_launch); otherwise the
-    library GEMM batched over token chunks + a small sum, counted as a library fallback.  db is
-    None unless with_db.  gelu_x: x holds the fc1 pre-activation h and the kernel contracts with
-    GELU(h) (hvk_weight_grad_gelu_x; callers check support).  xshift (f32 [K]) or None:
-    dW = g^T (x + 1 xshift^T) (hvk_weight_grad_shift; the proj Linear's folded v_bias)."""
+    one pass over g) for every SwinV2 shape it is built for, any M (_dw_launch) -- on the
+    weight-gradient side stream when `leaves` (the parameters whose gradients dW / db are) allow it
+    (wgrad_stream_scope); otherwise the library GEMM batched over token chunks + a small sum,
+    counted as a library fallback.  db is None unless with_db.  gelu_x: x holds the fc1
+    pre-activation h and the kernel contracts with GELU(h) (hvk_weight_grad_gelu_x; callers check
+    support).  xshift (f32 [K]) or None: dW = g^T (x + 1 xshift^T) (hvk_weight_grad_shift; the proj
+    Linear's folded v_bias)."""
     M, N = g.shape
     K = x.shape[1]
-    if gelu_x or _dw_native(M, N, K):
-        return _dw_launch(g, x, with_db, gelu_x, _f32(xshift) if xshift is not None else None, [])
+    if gelu_x or routes.dw(M, N, K):
+        xs = _f32(xshift) if xshift is not None else None
+        keep, outs = [xs], []
+        with _wgrad_side(leaves if g.is_cuda else (), keep, outs):
+            dw, db = _dw_launch(g, x, with_db, gelu_x, xs, keep)
+            outs += (dw, db)
+        return dw, db
     if xshift is not None:
         dw, db = weight_grad(g, x, True)
         dw.add_(torch.outer(db, _f32(xshift)))
@@ -450,109 +433,52 @@ def library_fallbacks(reset=False):
     return out
 
 
-_LIN_OK = {}
-_TILE_ANY = {}
-
-
-def _tile_any(M, K, N):
-    """libhvk's tiled GEMM takes the shape at all (hvk_gemm_supported: K % 64, 128 | N or 192 | N,
-    any M): the native route for shapes outside the measured speed rules of _tile_ok and the
-    skinny kernel's table (small microbatches), instead of the library GEMM."""
-    ok = _TILE_ANY.get((K, N))
-    if ok is None:
-        ok = _TILE_ANY[(K, N)] = bool(_lib.load().hvk_gemm_supported(1, K, N))
-    return ok and M > 0
-
-
-def _linear_native(M, K, N):
-    """True when libhvk's skinny MFMA GEMM is built for (K, N) (include/hvk.h)."""
-    key = (K, N)
-    ok = _LIN_OK.get(key)
-    if ok is None:
-        ok = bool(_lib.load().hvk_linear_supported(max(M, 1), K, N))
-        _LIN_OK[key] = ok
-    return ok and M > 0
-
-
-def _tile_ok(M, K, N):
-    """libhvk's tiled MFMA GEMM (hvk_gemm_fwd) where it measured faster than the library GEMM
-    (tools/bench_gemm.py): the stage-2 shapes (K <= 1536, fc2 forward and fc1 input gradient
-    included), the stage-1 shapes with 192 | N (K >= 192), and every stage-3 shape (and the
-    stage-2 PatchMerging) with 192 | N, on 128 x 192 tiles."""
-    if K % 64 or M <= 0:
-        return False
-    if N % 128:  # the 128 x 192 tile: stage-1 qkv / proj / fc2 forward, qkv / fc1 input grads
-        return N % 192 == 0 and K >= 192 and M >= 32768
-    if M >= 8192 and N % 192 == 0:  # stage 3 and its PatchMerging (128 x 192 tiles)
-        return True
-    return (M >= 32768 and K <= 1536) or (K == 768 and N == 768)
+_tile_ok = routes.tile_ok  # the names tests and tools use
 
 
 def _native_nt(M, K, N):
     """True when mm_nt runs one of libhvk's GEMMs for this shape."""
-    return _tile_ok(M, K, N) or _linear_native(M, K, N) or _tile_any(M, K, N)
-
-
-def _dgrad_fallback(g2, wb):
-    """Input gradient g2 wb for a shape no libhvk GEMM takes (counted / strict, see
-    library_fallback)."""
-    library_fallback("dgrad", f"M={g2.shape[0]} N={wb.shape[0]} K={wb.shape[1]}")
-    return g2 @ wb
-
-
-def _gelu_skinny_k():
-    """fc1 + GELU widths on the skinny kernel (stage 0 outside the fused MLP; stage 1 unless
-    options.s1_gelu_tile routes it to the tiled EPI 1 kernel)."""
-    return (96,) if OPTIONS.s1_gelu_tile else (96, 192)
+    return routes.nt(M, K, N) is not None
 
 
 def gelu_fwd(x2, wb, bias):
-    """(h, GELU(h)) with h = x2 wb^T + bias as ONE kernel (fc1 of swinv2.py:58-62), or None
-    when no fused kernel is built for the shape."""
+    """(h, GELU(h)) with h = x2 wb^T + bias as ONE kernel (fc1 of swinv2.py:58-62); callers check
+    routes.gelu_fwd."""
     M, K = x2.shape
     N = wb.shape[0]
-    lib = _lib.load()
-    if (K in _gelu_skinny_k() or K in _skinny_first_k()) and lib.hvk_linear_gelu_supported(M, K, N):
-        fn = "hvk_linear_gelu_fwd"
-    elif _tile_any(M, K, N):
-        fn = "hvk_gemm_gelu_fwd"
-    else:
-        return None
+    fn = {"tile": "hvk_gemm_gelu_fwd", "skinny": "hvk_linear_gelu_fwd"}[routes.gelu_fwd(M, K, N)]
     h = torch.empty((M, N), device=x2.device, dtype=torch.bfloat16)
     y = torch.empty_like(h)
     call(fn, ptr(x2), ptr(wb), ptr(_f32(bias)), ptr(h), ptr(y), M, K, N, stream())
     return h, y
 
 
-def _skinny_first_k():
-    """SwinV2-B's stage 0-1 widths (K = 128 / 256): the skinny kernel before the tiled one."""
-    return (128, 256) if OPTIONS.skinny_b else ()
-
-
-def _skinny_first(M, K, N):
-    return K in _skinny_first_k() and _linear_native(M, K, N)
-
-
 def mm_nt(x2, wb, bias=None):
     """y = x2 wb^T (+ bias): libhvk's MFMA kernels -- skinny weight-stationary for the
     memory-bound stage 0-1 shapes, tiled for stages 2-3 (and any other shape the tile takes:
-    small microbatches) -- else the library GEMM, counted as a library fallback.  x2 [M, K]
-    bf16, wb [N, K] bf16, bias f32 [N]."""
+    small microbatches; routes.nt) -- else the library GEMM, counted as a library fallback.
+    x2 [M, K] bf16, wb [N, K] bf16, bias f32 [N]."""
     M, K = x2.shape
     N = wb.shape[0]
+    fn = {"tile": "hvk_gemm_fwd", "skinny": "hvk_linear_fwd"}.get(routes.nt(M, K, N))
+    if fn is None:
+        library_fallback("mm_nt", f"M={M} K={K} N={N}")
+        return F.linear(x2, wb, bias.to(torch.bfloat16) if bias is not None else None)
     b = _f32(bias) if bias is not None else None
-    if (_tile_ok(M, K, N) and not _skinny_first(M, K, N)) or (not _linear_native(M, K, N) and _tile_any(M, K, N)):
-        y = torch.empty((M, N), device=x2.device, dtype=torch.bfloat16)
-        call("hvk_gemm_fwd", ptr(x2), ptr(wb), ptr(b) if b is not None else None, ptr(y), M, K, N,
-             stream())
-        return y
-    if _linear_native(M, K, N):
-        y = torch.empty((M, N), device=x2.device, dtype=torch.bfloat16)
-        call("hvk_linear_fwd", ptr(x2), ptr(wb), ptr(b) if b is not None else None, ptr(y), M, K,
-             N, stream())
-        return y
-    library_fallback("mm_nt", f"M={M} K={K} N={N}")
-    return F.linear(x2, wb, bias.to(torch.bfloat16) if bias is not None else None)
+    y = torch.empty((M, N), device=x2.device, dtype=torch.bfloat16)
+    call(fn, ptr(x2), ptr(wb), ptr(b) if b is not None else None, ptr(y), M, K, N, stream())
+    return y
+
+
+def _dgrad(g2, wb, wt):
+    """Input gradient g2 wb of a Linear with weight wb [N, K] (wt: its prepared transpose or
+    None): mm_nt on the transpose, or the library GEMM for a shape no libhvk GEMM takes (counted /
+    strict, see library_fallback)."""
+    N, K = wb.shape
+    if routes.nt(g2.shape[0], N, K) is None:
+        library_fallback("dgrad", f"M={g2.shape[0]} N={N} K={K}")
+        return g2 @ wb
+    return mm_nt(g2, _bf16_t(wb, wt))
 
 
 class LinearFn(torch.autograd.Function):
@@ -581,8 +507,7 @@ class LinearFn(torch.autograd.Function):
         g2 = _bf16(gy).reshape(-1, N)
         gx = None
         if ctx.needs_input_grad[0]:
-            gx = (mm_nt(g2, _bf16_t(wb, ctx.wt)) if _native_nt(g2.shape[0], N, K)
-                  else _dgrad_fallback(g2, wb)).reshape(xb.shape)
+            gx = _dgrad(g2, wb, ctx.wt).reshape(xb.shape)
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
         dw, db = None, None
         if ctx.needs_input_grad[1]:
@@ -609,19 +534,17 @@ def qkv_nt(x2, wb, bias, scale):
     mm_nt + hvk_qk_normalize in place."""
     M, K = x2.shape
     N = wb.shape[0]
-    lib = _lib.load()
     y = torch.empty((M, N), device=x2.device, dtype=torch.bfloat16)
     rn = torch.empty((M, 2 * N // 96), device=x2.device, dtype=torch.float32)
     b = ptr(_f32(bias)) if bias is not None else None
     sc = _f32(scale.detach())  # its gradient comes from the attention core (logit = scale cos)
-    skinny = _linear_native(M, K, N) and lib.hvk_linear_qkv_supported(M, K, N)
-    if N % 96 == 0 and ((_tile_ok(M, K, N) and not _skinny_first(M, K, N)) or (not skinny and _tile_any(M, K, N))):
-        call("hvk_gemm_qkv_fwd", ptr(x2), ptr(wb), b, ptr(y), ptr(rn), ptr(sc), M, K, N, stream())
-    elif skinny:
-        call("hvk_linear_qkv_fwd", ptr(x2), ptr(wb), b, ptr(y), ptr(rn), ptr(sc), M, K, N, stream())
-    else:
+    route = routes.qkv(M, K, N)
+    if route == "normalize":
         y = mm_nt(x2, wb, bias)
         call("hvk_qk_normalize", ptr(y), ptr(rn), ptr(sc), M, N // 3, stream())
+    else:
+        call("hvk_gemm_qkv_fwd" if route == "tile" else "hvk_linear_qkv_fwd", ptr(x2), ptr(wb), b, ptr(y), ptr(rn),
+             ptr(sc), M, K, N, stream())
     return y, rn
 
 
@@ -669,7 +592,6 @@ def linear_qkv(x, weight, bias, scale):
 
 
 # --------------------------------------------------------------------------- classifier head
-_HEAD_WS = {}
 _HEAD_W = {}  # device -> (key, concatenated bf16 tier weights): rebuilt only when a weight changes
 
 
@@ -741,10 +663,7 @@ class HeadFn(torch.autograd.Function):
         dw = torch.empty((Np, K), device=xb.device, dtype=torch.float32) if (want_w or want_b) else None
         db = torch.empty(Np, device=xb.device, dtype=torch.float32) if want_b else None
         nb = _lib.load().hvk_head_bwd_workspace_bytes(M, K, Np) if want_x else 0
-        key = (xb.device, nb)
-        wsb = _HEAD_WS.get(key)
-        if nb and wsb is None:
-            wsb = _HEAD_WS[key] = torch.empty(nb // 4, device=xb.device, dtype=torch.float32)
+        wsb = _workspace("head", xb.device, nb) if nb else None
         call("hvk_head_bwd", ptr(g), ptr(xb), ptr(wcat), ptr(gx) if want_x else None, ptr(dw) if dw is not None else None,
              ptr(db) if want_b else None, M, K, Np, ptr(wsb) if nb else None, nb, stream())
         dws, dbs, off = [], [], 0
@@ -819,20 +738,6 @@ def attn_biases(q_bias, v_bias, proj_bias, proj_w):
 
 
 # --------------------------------------------------------------------------- W-MSA
-_WMSA_WS = {}
-
-
-def _wmsa_workspace(device, nbytes):
-    """Persistent zero-filled W-MSA backward workspace (the kernels leave it zero again,
-    include/hvk.h), one per device and size: no memset per call."""
-    key = (device, nbytes)
-    ws = _WMSA_WS.get(key)
-    if ws is None:
-        ws = torch.zeros(nbytes // 4, device=device, dtype=torch.float32)
-        _WMSA_WS[key] = ws
-    return ws
-
-
 class WindowAttentionCore(torch.autograd.Function):
     """Shifted-window cosine attention core on un-partitioned tokens.
 
@@ -880,9 +785,6 @@ class WindowAttentionCore(torch.autograd.Function):
         saved = ctx.saved_tensors
         qkv, bias_table, scale = saved[:3]
         B, H, W, C, nh, win, shift = ctx.geom
-        if len(saved) == 4:
-            return WindowAttentionCore._backward_normed(ctx, dout, qkv, bias_table, scale, saved[3])
-        out, lse = saved[3:] if len(saved) == 5 else (None, None)
         dout = _bf16(dout)
         dqkv = torch.empty_like(qkv)
         dtab = torch.empty_like(bias_table)
@@ -890,26 +792,14 @@ class WindowAttentionCore(torch.autograd.Function):
         dqb = (torch.empty(C, device=qkv.device, dtype=torch.float32)
                if ctx.has_q_bias and ctx.needs_input_grad[1] else None)
         ws_bytes = _lib.load().hvk_wmsa_bwd_workspace_bytes(nh, win)
-        ws = _wmsa_workspace(qkv.device, ws_bytes)
-        call("hvk_wmsa_bwd", ptr(qkv), ptr(dout), ptr(out), ptr(lse), ptr(dqkv),
-             ptr(dqb) if dqb is not None else None, ptr(bias_table), ptr(scale), ptr(dtab),
-             ptr(dscale), ptr(ws), ws_bytes, B, H, W, C, nh, win, shift, stream())
-        return dqkv, dqb, dtab, dscale, None, None, None, None, None, None
-
-    @staticmethod
-    def _backward_normed(ctx, dout, qkv, bias_table, scale, rn):
-        B, H, W, C, nh, win, shift = ctx.geom
-        dout = _bf16(dout)
-        dqkv = torch.empty_like(qkv)
-        dtab = torch.empty_like(bias_table)
-        dscale = torch.empty_like(scale)
-        dqb = (torch.empty(C, device=qkv.device, dtype=torch.float32)
-               if ctx.has_q_bias and ctx.needs_input_grad[1] else None)
-        ws_bytes = _lib.load().hvk_wmsa_bwd_workspace_bytes(nh, win)
-        ws = _wmsa_workspace(qkv.device, ws_bytes)
-        call("hvk_wmsa_bwd_normed", ptr(qkv), ptr(rn), ptr(dout), ptr(dqkv),
-             ptr(dqb) if dqb is not None else None, ptr(bias_table), ptr(scale), ptr(dtab),
-             ptr(dscale), ptr(ws), ws_bytes, B, H, W, C, nh, win, shift, stream())
+        ws = _workspace("wmsa", qkv.device, ws_bytes, zero=True)
+        tail = (ptr(dqkv), ptr(dqb) if dqb is not None else None, ptr(bias_table), ptr(scale), ptr(dtab),
+                ptr(dscale), ptr(ws), ws_bytes, B, H, W, C, nh, win, shift, stream())
+        if len(saved) == 4:  # (q^, k^, v) and rn from linear_qkv
+            call("hvk_wmsa_bwd_normed", ptr(qkv), ptr(saved[3]), ptr(dout), *tail)
+        else:
+            out, lse = saved[3:] if len(saved) == 5 else (None, None)
+            call("hvk_wmsa_bwd", ptr(qkv), ptr(dout), ptr(out), ptr(lse), *tail)
         return dqkv, dqb, dtab, dscale, None, None, None, None, None, None
 
 
@@ -924,9 +814,6 @@ def window_attention_core(qkv, bias_table, scale, H, W, num_heads, window, shift
 
 
 # --------------------------------------------------------------------------- CPB table
-_CPB_WS = {}
-
-
 class CpbTable(torch.autograd.Function):
     """(table [nH, RR], scale [nH]) = (16 sigmoid(cpb_mlp(coords)) transposed, exp(clamp(
     logit_scale))) in one launch (hvk_cpb_fwd); backward two launches (hvk_cpb_bwd).
@@ -958,10 +845,7 @@ class CpbTable(torch.autograd.Function):
         dw1, db1, dw2 = torch.empty_like(w1), torch.empty_like(b1), torch.empty_like(w2)
         dlogit = torch.empty_like(logit)
         nbytes = _lib.load().hvk_cpb_bwd_workspace_bytes(RR, nH)
-        key = (w1.device, nbytes)
-        ws = _CPB_WS.get(key)
-        if ws is None:
-            ws = _CPB_WS[key] = torch.empty(nbytes // 4, device=w1.device, dtype=torch.float32)
+        ws = _workspace("cpb", w1.device, nbytes)
         call("hvk_cpb_bwd", ptr(coords), ptr(w1), ptr(b1), ptr(w2), ptr(logit), ctx.clamp_max, RR,
              nH, hid, ptr(table), ptr(dtable), ptr(dscale), ptr(dw1), ptr(db1), ptr(dw2),
              ptr(dlogit), ptr(ws), nbytes, stream())
@@ -1026,21 +910,14 @@ class BlockTables(torch.autograd.Function):
         dw1, db1, dw2 = torch.empty_like(w1), torch.empty_like(b1), torch.empty_like(w2)
         dlogit = torch.empty_like(logit)
         nbytes = _lib.load().hvk_cpb_bwd_workspace_bytes(RR, nH)
-        key = (w1.device, nbytes)
-        ws = _CPB_WS.get(key)
-        if ws is None:
-            ws = _CPB_WS[key] = torch.empty(nbytes // 4, device=w1.device, dtype=torch.float32)
+        ws = _workspace("cpb", w1.device, nbytes)
         # parameter gradients only: on the weight-gradient side stream when enabled
-        fork = _wgrad_fork(ctx.leaves)
-        with torch.cuda.stream(fork[1]) if fork else contextlib.nullcontext():
+        with _wgrad_side(ctx.leaves, (g_eff, v, pw, coords, w1, b1, w2, logit, table, dtable, dscale),
+                         (dpb, dv, dpw, dw1, db1, dw2, dlogit)):
             call("hvk_block_bias_bwd", ptr(g_eff), ptr(v), ptr(pw), C, ptr(dpb), ptr(dv), ptr(dpw),
                  ptr(coords), ptr(w1), ptr(b1), ptr(w2), ptr(logit), ctx.clamp_max, RR, nH, hid, ptr(table),
                  ptr(dtable), ptr(dscale), ptr(dw1), ptr(db1), ptr(dw2), ptr(dlogit), ptr(ws), nbytes,
                  stream())
-        if fork:
-            _wgrad_joined((g_eff, v, pw, coords, w1, b1, w2, logit, table, dtable, dscale),
-                          (dpb, dv, dpw, dw1, db1, dw2, dlogit))
-            _wgrad_outputs(dv, dpb, dpw, dw1, db1, dw2)
         return (dv, dpb, dpw, None, dw1, db1, dw2, dlogit.reshape(ctx.logit_shape), None, None)
 
 
@@ -1060,10 +937,7 @@ class LayerNormResidual(torch.autograd.Function):
         C = a.shape[-1]
         rows = a.numel() // C
         a = _bf16(a)
-        gamma, beta = _f32(gamma), _f32(beta)
-        abias = _f32(abias) if abias is not None else None
-        x0 = _f32(x0) if x0 is not None else None
-        sample_scale = _f32(sample_scale) if sample_scale is not None else None
+        abias, x0, gamma, beta, sample_scale = _ln_operands(abias, x0, gamma, beta, sample_scale)
         x = torch.empty(a.shape, device=a.device, dtype=torch.float32)
         xb = torch.empty(a.shape, device=a.device, dtype=torch.bfloat16)
         mean = torch.empty(rows, device=a.device, dtype=torch.float32)
@@ -1109,17 +983,19 @@ def _ln_residual_bwd(a, abias, gamma, sample_scale, mean, rstd, rps, has_x0, gx,
     dabias = torch.empty_like(gamma) if abias is not None else None
     ws_bytes = _lib.load().hvk_ln_bwd_workspace_bytes(C)
     ws = torch.empty(ws_bytes // 4, device=a.device, dtype=torch.float32)
-    fork = _wgrad_fork(leaves) if a.is_cuda and OPTIONS.wgrad_stream_ln else None
-    if fork is None:
-        call("hvk_ln_residual_bwd", ptr(a), ptr(abias), ptr(gamma), ptr(sample_scale), ptr(mean),
-             ptr(rstd), ptr(gx), ptr(gxb), rows, C, rps, ptr(gx0), ptr(ga), ptr(dgamma),
-             ptr(dbeta), ptr(dabias), ptr(ws), ws_bytes, stream())
-        return ga, dabias, gx0, dgamma, dbeta
-    call("hvk_ln_residual_bwd_split", ptr(a), ptr(abias), ptr(gamma), ptr(sample_scale), ptr(mean),
-         ptr(rstd), ptr(gx), ptr(gxb), rows, C, rps, ptr(gx0), ptr(ga), ptr(dgamma),
-         ptr(dbeta), ptr(dabias), ptr(ws), ws_bytes, stream(), ctypes.c_void_p(fork[1].cuda_stream))
-    _wgrad_joined((ws,), (dgamma, dbeta, dabias))
+    args = (ptr(a), ptr(abias), ptr(gamma), ptr(sample_scale), ptr(mean), ptr(rstd), ptr(gx), ptr(gxb), rows, C, rps,
+            ptr(gx0), ptr(ga), ptr(dgamma), ptr(dbeta), ptr(dabias), ptr(ws), ws_bytes, stream())
+    with _wgrad_side(leaves if a.is_cuda and OPTIONS.wgrad_stream_ln else (), (ws,), (dgamma, dbeta, dabias)) as side:
+        if side is None:
+            call("hvk_ln_residual_bwd", *args)
+        else:  # the row kernel stays on the main stream (args), the column sums go to the side stream
+            call("hvk_ln_residual_bwd_split", *args, ctypes.c_void_p(side.cuda_stream))
     return ga, dabias, gx0, dgamma, dbeta
+
+
+def _ln_operands(abias, x0, gamma, beta, sample_scale):
+    """The post-norm's operands as the kernels read them: contiguous f32, None kept."""
+    return tuple(_f32(t) if t is not None else None for t in (abias, x0, gamma, beta, sample_scale))
 
 
 def _ln_out(a, rows):
@@ -1146,10 +1022,7 @@ class LinearLNFn(torch.autograd.Function):
         M = xin.numel() // K
         a = torch.empty((*xin.shape[:-1], N), device=xin.device, dtype=torch.bfloat16)
         x, xb, mean, rstd = _ln_out(a, M)
-        gamma, beta = _f32(gamma), _f32(beta)
-        abias = _f32(abias) if abias is not None else None
-        x0 = _f32(x0) if x0 is not None else None
-        sample_scale = _f32(sample_scale) if sample_scale is not None else None
+        abias, x0, gamma, beta, sample_scale = _ln_operands(abias, x0, gamma, beta, sample_scale)
         call("hvk_linear_ln_fwd", ptr(xin), ptr(wb), M, K, N, ptr(abias), ptr(x0), ptr(gamma), ptr(beta),
              ptr(sample_scale), rows_per_sample, float(eps), ptr(a), ptr(x), ptr(xb), ptr(mean), ptr(rstd),
              stream())
@@ -1174,8 +1047,7 @@ class LinearLNFn(torch.autograd.Function):
         g2 = ga.reshape(-1, N)
         gin = None
         if ctx.needs_input_grad[0]:
-            gin = (mm_nt(g2, _bf16_t(wb, ctx.wt)) if _native_nt(g2.shape[0], N, K)
-                   else _dgrad_fallback(g2, wb)).reshape(xin.shape)
+            gin = _dgrad(g2, wb, ctx.wt).reshape(xin.shape)
         dw = (weight_grad(g2, xin.reshape(-1, K), False, xshift=ctx.xshift, leaves=ctx.leaves)[0]
               if ctx.needs_input_grad[1] else None)
         return gin, dw, None, dabias, gx0, dgamma, dbeta, None, None, None
@@ -1184,8 +1056,7 @@ class LinearLNFn(torch.autograd.Function):
 def linear_ln_supported(M, K, N):
     """The fused Linear + post-norm (hvk_linear_ln_fwd) is built for this shape and enabled
     (options.ln_epilogue; the C = 192 tile form also options.ln_epilogue_tile)."""
-    return (OPTIONS.ln_epilogue and (N == 96 or OPTIONS.ln_epilogue_tile)
-            and bool(_lib.load().hvk_linear_ln_supported(M, K, N)))
+    return routes.linear_ln(M, K, N) is not None
 
 
 def linear_ln(inp, weight, x0, gamma, beta, sample_scale=None, rows_per_sample=1, eps=1e-5, abias=None,
@@ -1303,8 +1174,7 @@ class LinearGelu(torch.autograd.Function):
              stream())
         gx = None
         if ctx.needs_input_grad[0]:
-            gx = (mm_nt(gh, _bf16_t(wb, ctx.wt)) if _native_nt(M, N, K)
-                  else _dgrad_fallback(gh, wb)).reshape(xb.shape)
+            gx = _dgrad(gh, wb, ctx.wt).reshape(xb.shape)
         dw = weight_grad(gh, xb.reshape(-1, K), leaves=ctx.leaves)[0] if ctx.needs_input_grad[1] else None
         return gx, dw, db
 
@@ -1313,18 +1183,15 @@ def linear_gelu(x, weight, bias):
     """GELU(F.linear(x, weight, bias)): fused kernel where built, else GEMM + activation kernel."""
     N, K = weight.shape
     M = x.numel() // K
-    if bias is not None and (((K in (96, 192) or K in _skinny_first_k())
-                              and _lib.load().hvk_linear_gelu_supported(M, K, N)) or _tile_any(M, K, N)):
+    if bias is not None and routes.gelu_fwd(M, K, N) is not None:
         return LinearGelu.apply(x, weight, bias)
     return bias_gelu(linear(x, weight), bias)
 
 
 class MlpFn(torch.autograd.Function):
-    """fc2(GELU(fc1(x))) (swinv2.py:58-65 with drop = 0): forward = the fused fc1 + GELU kernel
-    and the fc2 GEMM; backward runs fc2's input gradient and the activation backward as ONE
-    kernel (hvk_linear_gelu_bwd; the tiled hvk_gemm_gelu_bwd for stage 2) instead of GEMM ->
-    bf16 dy1 -> activation kernel, and the fc1 bias gradient rides on fc1's weight-gradient
-    kernel.  fc2's bias, when given, is added by the GEMM (else folded downstream)."""
+    """fc2(GELU(fc1(x))) (swinv2.py:58-65 with drop = 0) by the plan of routes.mlp: forward = the
+    fused fc1 + GELU kernel and the fc2 GEMM (stage 0: one kernel, hvk_mlp_fwd); backward
+    _mlp_backward.  fc2's bias, when given, is added by the GEMM (else folded downstream)."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2):
@@ -1336,16 +1203,15 @@ class MlpFn(torch.autograd.Function):
         N2 = w2b.shape[0]
         x2 = xb.reshape(-1, K)
         M = x2.shape[0]
-        ctx.recompute = _gelu_recompute(M, K, N1, N2)
-        if ctx.recompute:
+        ctx.plan = routes.mlp(M, K, N1, N2)
+        if ctx.plan == "recompute":
             # GELU(h) is never stored: fc2 and its weight gradient recompute it per fragment
-            h = mm_nt(x2, w1b, b1)
+            h, y1 = mm_nt(x2, w1b, b1), None
             y = torch.empty((M, N2), device=x2.device, dtype=torch.bfloat16)
             b = _f32(b2) if b2 is not None else None
             call("hvk_linear_gelu_in_fwd", ptr(h), ptr(w2b), ptr(b) if b is not None else None, ptr(y), M,
                  N1, N2, stream())
-            ctx.save_for_backward(xb, w1b, w2b, h)
-        elif OPTIONS.mlp_fused and _lib.load().hvk_mlp_fwd_supported(M, K, N1, N2):
+        elif ctx.plan == "fused":
             # stage-0 width: fc1 + GELU + fc2 in one kernel (no re-read of GELU(h))
             h = torch.empty((M, N1), device=x2.device, dtype=torch.bfloat16)
             y1 = torch.empty_like(h)
@@ -1353,11 +1219,10 @@ class MlpFn(torch.autograd.Function):
             b = _f32(b2) if b2 is not None else None
             call("hvk_mlp_fwd", ptr(x2), ptr(w1b), ptr(_f32(b1)), ptr(w2b), ptr(b) if b is not None else None,
                  ptr(h), ptr(y1), ptr(y), M, K, N1, N2, stream())
-            ctx.save_for_backward(xb, w1b, w2b, h, y1)
         else:
             h, y1 = gelu_fwd(x2, w1b, b1)
             y = mm_nt(y1, w2b, b2)
-            ctx.save_for_backward(xb, w1b, w2b, h, y1)
+        ctx.save_for_backward(xb, w1b, w2b, h, y1)
         ctx.has_b2 = b2 is not None
         ctx.leaves = ((w1, b1), (w2, b2))
         note_leaf_uses(_flat(ctx.leaves), ctx)
@@ -1365,51 +1230,50 @@ class MlpFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        if ctx.recompute:
-            xb, w1b, w2b, h = ctx.saved_tensors
+        return _mlp_backward(ctx.plan, gy, *ctx.saved_tensors, ctx.wts, ctx.needs_input_grad[0], ctx.has_b2,
+                             ctx.leaves)
+
+
+def _mlp_backward(plan, gy, xb, w1b, w2b, h, y1, wts, want_x, has_b2, leaves):
+    """The MLP's backward after the forward plan `plan` (routes.mlp / routes.mlp_ln): (gx, dW1,
+    db1, dW2, db2).  fc2's weight gradient first (contracting with GELU(h) recomputed from h under
+    "recompute"; its bias gradient only with has_b2 -- under an LN epilogue that is the norm's
+    dabias); then both input gradients as ONE kernel at the stage-0 width (hvk_mlp_bwd: fc2's
+    through GELU' and fc1's, gh stored for fc1's weight gradient, not re-read for gx), else fc2's
+    input gradient and the activation backward as one kernel (routes.gelu_bwd) instead of GEMM ->
+    bf16 dy1 -> activation kernel, and fc1's (_dgrad); fc1's bias gradient rides on its
+    weight-gradient kernel."""
+    N1, K = w1b.shape
+    N2 = w2b.shape[0]
+    g2 = _bf16(gy).reshape(-1, N2)
+    M = g2.shape[0]
+    recompute = plan == "recompute"
+    dw2, db2 = weight_grad(g2, h if recompute else y1, has_b2, gelu_x=recompute, leaves=leaves[1])
+    gh = torch.empty_like(h)
+    w2t = _bf16_t(w2b, wts[1])
+    gx = None
+    if want_x and not recompute and routes.mlp_bwd_fused(M, K, N1, N2):
+        gx = torch.empty((M, K), device=h.device, dtype=torch.bfloat16)
+        call("hvk_mlp_bwd", ptr(g2), ptr(w2t), ptr(h), ptr(_bf16_t(w1b, wts[0])), ptr(gh), ptr(gx), M, N2, N1, K,
+             stream())
+    else:
+        if routes.gelu_bwd(M, N2, N1) == "skinny":
+            call("hvk_linear_gelu_bwd", ptr(g2), ptr(w2t), ptr(h), ptr(gh), None, M, N2, N1, stream())
         else:
-            xb, w1b, w2b, h, y1 = ctx.saved_tensors
-        N1, K = w1b.shape
-        N2 = w2b.shape[0]
-        g2 = _bf16(gy).reshape(-1, N2)
-        M = g2.shape[0]
-        if ctx.recompute:
-            dw2, db2 = weight_grad(g2, h, ctx.has_b2, gelu_x=True, leaves=ctx.leaves[1])
-        else:
-            dw2, db2 = weight_grad(g2, y1, ctx.has_b2, leaves=ctx.leaves[1])
-        gh = torch.empty_like(h)
-        w2t = _bf16_t(w2b, ctx.wts[1])
-        if (OPTIONS.mlp_fused and ctx.needs_input_grad[0] and not ctx.recompute
-                and _lib.load().hvk_mlp_bwd_supported(M, N2, N1, K)):
-            # stage-0 width: fc2's input gradient through GELU' and fc1's input gradient in one
-            # kernel (gh stored for fc1's weight gradient, not re-read for gx)
-            gx = torch.empty((M, K), device=h.device, dtype=torch.bfloat16)
-            call("hvk_mlp_bwd", ptr(g2), ptr(w2t), ptr(h), ptr(_bf16_t(w1b, ctx.wts[0])), ptr(gh), ptr(gx),
-                 M, N2, N1, K, stream())
-            dw1, db1 = weight_grad(gh, xb.reshape(-1, K), True, leaves=ctx.leaves[0])  # fc1 bias gradient fused
-            return gx.reshape(xb.shape), dw1, db1, dw2, db2
-        lib = _lib.load()
-        if ((_tile_ok(M, N2, N1) and not (N2 in _skinny_first_k() and lib.hvk_linear_gelu_bwd_supported(M, N2, N1)))
-                or not lib.hvk_linear_gelu_bwd_supported(M, N2, N1)):
             call("hvk_gemm_gelu_bwd", ptr(g2), ptr(w2t), ptr(h), ptr(gh), M, N2, N1, stream())
-        else:
-            call("hvk_linear_gelu_bwd", ptr(g2), ptr(w2t), ptr(h), ptr(gh), None, M, N2, N1,
-                 stream())
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = (mm_nt(gh, _bf16_t(w1b, ctx.wts[0])) if _native_nt(M, N1, K)
-                  else _dgrad_fallback(gh, w1b)).reshape(xb.shape)
-        dw1, db1 = weight_grad(gh, xb.reshape(-1, K), True, leaves=ctx.leaves[0])  # fc1 bias gradient fused
-        return gx, dw1, db1, dw2, db2
+        if want_x:
+            gx = _dgrad(gh, w1b, wts[0])
+    dw1, db1 = weight_grad(gh, xb.reshape(-1, K), True, leaves=leaves[0])
+    return gx.reshape(xb.shape) if want_x else None, dw1, db1, dw2, db2
 
 
 class MlpLNFn(torch.autograd.Function):
-    """(x, xb) = LayerNormResidual(fc2(GELU(fc1(inp))), abias = fc2's bias, x0, ...).  Stage-0
-    width: ONE kernel forward (hvk_mlp_ln_fwd: the fused MLP with the block's norm2 in its
-    epilogue, bit-identical to hvk_mlp_fwd + hvk_ln_residual_fwd).  Stage-1 width (N2 = 192):
-    fc1 + GELU as MlpFn's kernel, fc2 on the 128 x 192 tile with the norm in its epilogue
-    (hvk_linear_ln_fwd).  Backward = the LayerNorm backward, then MlpFn's chain for the path taken
-    (fc2's bias gradient is the norm's dabias)."""
+    """(x, xb) = LayerNormResidual(fc2(GELU(fc1(inp))), abias = fc2's bias, x0, ...) by the plan of
+    routes.mlp_ln.  "fused", the stage-0 width: ONE kernel forward (hvk_mlp_ln_fwd: the fused MLP
+    with the block's norm2 in its epilogue, bit-identical to hvk_mlp_fwd + hvk_ln_residual_fwd).
+    "chain", the stage-1 width (N2 = 192): fc1 + GELU as MlpFn's kernel, fc2 on the 128 x 192 tile
+    with the norm in its epilogue (hvk_linear_ln_fwd).  Backward = the LayerNorm backward, then
+    _mlp_backward (fc2's bias gradient is the norm's dabias)."""
 
     @staticmethod
     def forward(ctx, inp, w1, b1, w2, abias, x0, gamma, beta, sample_scale, rows_per_sample, eps):
@@ -1424,13 +1288,10 @@ class MlpLNFn(torch.autograd.Function):
         M = x2.shape[0]
         a = torch.empty((*xin.shape[:-1], N2), device=xin.device, dtype=torch.bfloat16)
         x, xb, mean, rstd = _ln_out(a, M)
-        gamma, beta = _f32(gamma), _f32(beta)
-        abias = _f32(abias) if abias is not None else None
-        x0 = _f32(x0) if x0 is not None else None
-        sample_scale = _f32(sample_scale) if sample_scale is not None else None
+        abias, x0, gamma, beta, sample_scale = _ln_operands(abias, x0, gamma, beta, sample_scale)
         ln_args = (ptr(abias), ptr(x0), ptr(gamma), ptr(beta), ptr(sample_scale), rows_per_sample, float(eps))
-        ctx.fused = bool(_lib.load().hvk_mlp_ln_supported(M, K, N1, N2))
-        if ctx.fused:
+        ctx.plan = routes.mlp_ln(M, K, N1, N2)
+        if ctx.plan == "fused":
             h = torch.empty((M, N1), device=x2.device, dtype=torch.bfloat16)
             y1 = torch.empty_like(h)
             call("hvk_mlp_ln_fwd", ptr(x2), ptr(w1b), ptr(_f32(b1)), ptr(w2b), ptr(h), ptr(y1), ptr(a), M, K, N1,
@@ -1455,70 +1316,15 @@ class MlpLNFn(torch.autograd.Function):
         if r is None:
             return (None,) * 11
         ga, dabias, gx0, dgamma, dbeta = r
-        bwd = _mlp_bwd if ctx.fused else _mlp_bwd_tiled
-        gin, dw1, db1, dw2 = bwd(ga, xin, w1b, w2b, h, y1, ctx.wts, ctx.needs_input_grad[0], ctx.leaves)
+        gin, dw1, db1, dw2, _ = _mlp_backward(ctx.plan, ga, xin, w1b, w2b, h, y1, ctx.wts, ctx.needs_input_grad[0],
+                                              False, ctx.leaves)
         return gin, dw1, db1, dw2, dabias, gx0, dgamma, dbeta, None, None, None
 
 
-def _mlp_bwd(gy, xb, w1b, w2b, h, y1, wts, want_x, leaves=((), ())):
-    """MlpFn's backward at the stage-0 width (the fused hvk_mlp_bwd chain; fc2's bias gradient is
-    the caller's): (gx, dW1, db1, dW2)."""
-    N1, K = w1b.shape
-    N2 = w2b.shape[0]
-    g2 = _bf16(gy).reshape(-1, N2)
-    M = g2.shape[0]
-    dw2 = weight_grad(g2, y1, leaves=leaves[1])[0]
-    gh = torch.empty_like(h)
-    w2t = _bf16_t(w2b, wts[1])
-    gx = None
-    if want_x:
-        gx = torch.empty((M, K), device=h.device, dtype=torch.bfloat16)
-        call("hvk_mlp_bwd", ptr(g2), ptr(w2t), ptr(h), ptr(_bf16_t(w1b, wts[0])), ptr(gh), ptr(gx), M, N2, N1, K,
-             stream())
-        gx = gx.reshape(xb.shape)
-    else:
-        call("hvk_linear_gelu_bwd", ptr(g2), ptr(w2t), ptr(h), ptr(gh), None, M, N2, N1, stream())
-    dw1, db1 = weight_grad(gh, xb.reshape(-1, K), True, leaves=leaves[0])  # fc1 bias gradient fused
-    return gx, dw1, db1, dw2
-
-
-def _mlp_bwd_tiled(gy, xb, w1b, w2b, h, y1, wts, want_x, leaves=((), ())):
-    """MlpFn's unfused backward chain (fc2's input gradient through GELU' as one kernel, fc1's
-    input gradient, both weight gradients; fc2's bias gradient is the caller's): (gx, dW1, db1,
-    dW2)."""
-    N1, K = w1b.shape
-    N2 = w2b.shape[0]
-    g2 = _bf16(gy).reshape(-1, N2)
-    M = g2.shape[0]
-    dw2 = weight_grad(g2, y1, leaves=leaves[1])[0]
-    gh = torch.empty_like(h)
-    w2t = _bf16_t(w2b, wts[1])
-    lib = _lib.load()
-    if ((_tile_ok(M, N2, N1) and not (N2 in _skinny_first_k() and lib.hvk_linear_gelu_bwd_supported(M, N2, N1)))
-            or not lib.hvk_linear_gelu_bwd_supported(M, N2, N1)):
-        call("hvk_gemm_gelu_bwd", ptr(g2), ptr(w2t), ptr(h), ptr(gh), M, N2, N1, stream())
-    else:
-        call("hvk_linear_gelu_bwd", ptr(g2), ptr(w2t), ptr(h), ptr(gh), None, M, N2, N1, stream())
-    gx = None
-    if want_x:
-        gx = (mm_nt(gh, _bf16_t(w1b, wts[0])) if _native_nt(M, N1, K)
-              else _dgrad_fallback(gh, w1b)).reshape(xb.shape)
-    dw1, db1 = weight_grad(gh, xb.reshape(-1, K), True, leaves=leaves[0])  # fc1 bias gradient fused
-    return gx, dw1, db1, dw2
-
-
 def mlp_ln_supported(M, K, N1, N2):
-    """MlpLNFn applies: the fused stage-0 MLP + post-norm (hvk_mlp_ln_fwd and its fused backward
-    chain), or fc1 + GELU on MlpFn's kernels with fc2 + post-norm on the tile's LN epilogue."""
-    if not OPTIONS.ln_epilogue:
-        return False
-    lib = _lib.load()
-    if OPTIONS.mlp_fused and lib.hvk_mlp_ln_supported(M, K, N1, N2) and lib.hvk_mlp_bwd_supported(M, N2, N1, K):
-        return True
-    return (N2 != 96 and linear_ln_supported(M, N1, N2) and not _gelu_recompute(M, K, N1, N2)
-            and (((K in _gelu_skinny_k() or K in _skinny_first_k()) and lib.hvk_linear_gelu_supported(M, K, N1))
-                 or _tile_any(M, K, N1))
-            and (lib.hvk_linear_gelu_bwd_supported(M, N2, N1) or _tile_any(M, N2, N1)))
+    """MlpLNFn applies (routes.mlp_ln): the fused stage-0 MLP + post-norm, or fc1 + GELU on MlpFn's
+    kernels with fc2 + post-norm on the tile's LN epilogue."""
+    return routes.mlp_ln(M, K, N1, N2) is not None
 
 
 def mlp_ln(x, w1, b1, w2, x0, gamma, beta, sample_scale=None, rows_per_sample=1, eps=1e-5, abias=None):
@@ -1529,13 +1335,9 @@ def mlp_ln(x, w1, b1, w2, x0, gamma, beta, sample_scale=None, rows_per_sample=1,
 
 def mlp(x, w1, b1, w2, b2=None):
     """fc2(GELU(fc1(x))): the fused forward/backward kernels where built (skinny for stage 0-1,
-    tiled for stage 2-3), else linear_gelu + linear."""
+    tiled for stage 2-3; routes.mlp), else linear_gelu + linear."""
     N1, K = w1.shape
-    M = x.numel() // K
-    lib = _lib.load()
-    if (b1 is not None and (((K in (96, 192) or K in _skinny_first_k()) and lib.hvk_linear_gelu_supported(M, K, N1))
-                            or _tile_any(M, K, N1))
-            and (lib.hvk_linear_gelu_bwd_supported(M, w2.shape[0], N1) or _tile_any(M, w2.shape[0], N1))):
+    if b1 is not None and routes.mlp(x.numel() // K, K, N1, w2.shape[0]) is not None:
         return MlpFn.apply(x, w1, b1, w2, b2)
     return linear(linear_gelu(x, w1, b1), w2, b2)
 
@@ -1607,17 +1409,13 @@ def patch_merge_gather(x, H, W):
 def merge_linear_supported(B, H, W, C, N):
     """PatchMerging's gather folded into its reduction GEMM both ways (hvk_merge_*; option
     merge_gemm) for x [B, H*W, C] and the Linear 4C -> N."""
-    if not OPTIONS.merge_gemm:
-        return False
-    lib = _lib.load()
-    return bool(lib.hvk_merge_gemm_supported(B, H, W, C, N) and lib.hvk_merge_weight_grad_supported(B, H, W, C, N))
+    return routes.merge(B, H, W, C, N) is not None
 
 
 def merge_linear_ln_supported(B, H, W, C, N):
     """... and with PatchMerging's norm in the GEMM epilogue (N = 192; options ln_epilogue,
     ln_epilogue_tile)."""
-    return (merge_linear_supported(B, H, W, C, N) and OPTIONS.ln_epilogue and OPTIONS.ln_epilogue_tile
-            and bool(_lib.load().hvk_merge_linear_ln_supported(B, H, W, C, N)))
+    return routes.merge(B, H, W, C, N) == "ln"
 
 
 def _merge_linear_bwd(ctx, xb, wb, ga):
@@ -1635,12 +1433,8 @@ def _merge_linear_bwd(ctx, xb, wb, ga):
         nb = lib.hvk_weight_grad_workspace(M, N, 4 * C)
         ws = torch.empty(nb // 4, device=ga.device, dtype=torch.float32)
         dw = torch.empty((N, 4 * C), device=ga.device, dtype=torch.float32)
-        fork = _wgrad_fork(ctx.leaves)  # options.wgrad_stream: on the weight-gradient side stream
-        with torch.cuda.stream(fork[1]) if fork else contextlib.nullcontext():
+        with _wgrad_side(ctx.leaves, (ga, xb, ws), (dw,)):  # options.wgrad_stream: on the side stream
             call("hvk_merge_weight_grad", ptr(ga), ptr(xb), ptr(dw), B, H, W, C, N, ptr(ws), nb, stream())
-        if fork:
-            _wgrad_joined((ga, xb, ws), (dw,))
-            _wgrad_outputs(dw)
     return gx, dw
 
 

@@ -187,3 +187,26 @@ def test_side_stream_buffers_reused_with_host_ahead():
     for n, g in last.items():
         if n.split(".")[-2:] in EXACT:
             assert torch.equal(g.view(torch.int32), ref[n].view(torch.int32)), n
+
+
+def test_side_outputs_recorded_before_an_immediate_join():
+    """Outside a backward the side stream is joined at once, which forgets the side-written
+    addresses: the outputs of that very launch must have been recorded before, not after, or their
+    addresses stay behind and a later current-stream gradient reusing one would be taken for
+    side-written (the bucket hook would skip its wait)."""
+    from hvamd import ops, options
+    torch.manual_seed(0)
+    w = torch.nn.Parameter(torch.randn(96, 96, device="cuda"))
+    g = torch.randn(64, 96, device="cuda").bfloat16()
+    x = torch.randn(64, 96, device="cuda").bfloat16()
+    ops.reset_leaf_uses()
+    f0 = ops.wgrad_fork_count()
+    with options.override(wgrad_stream=True), ops.wgrad_stream_scope():
+        ops.linear(x, w)  # one forward use of the leaf: the fork takes it
+        dw, _ = ops.weight_grad(g, x, leaves=(w,))
+        assert ops.wgrad_fork_count() == f0 + 1  # it did run on the side stream
+        assert not ops.wgrad_produced_on_side(dw)
+        assert not ops._WgradStream.produced
+    torch.cuda.synchronize()
+    ref = g.double().t() @ x.double()
+    assert ((dw.double() - ref).norm() / ref.norm()).item() < 1e-6
