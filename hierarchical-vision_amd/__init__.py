@@ -8,6 +8,7 @@ Modules mirror the reference files they replace:
   algorithmic.py <- algorithmic.py (LabelSmoothing for list outputs)
   configs.py     <- configs.py     (structured config schema)
   simpleshot.py  <- simpleshot.py  (nearest-centroid evaluation of frozen features, flat / hierarchical)
+  linear_probe.py <- linear_probe.py (StandardScaler + one-vs-rest logistic fit + grid search, on the device)
   ddp.py            RCCL gradient all-reduce, bucketed, overlapped with backward
   ops.py            autograd Functions over the C ABI of libhvk.so
   _lib.py           ctypes binding of libhvk.so (include/hvk.h)

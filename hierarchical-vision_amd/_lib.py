@@ -127,10 +127,16 @@ SIGNATURES = {
     "hvk_ss_predict_flat_workspace": (_sz, [_i, _i]),
     "hvk_ss_predict_flat": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _sz, _p]),
     "hvk_ss_predict_tree": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "hvk_lp_moments": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
+    "hvk_lp_standardize": (_i, [_p, _i, _i, _i, _p, _p, ctypes.c_longlong, _p, _p, _p, _p]),
+    "hvk_lp_loss_grad_workspace": (_sz, [_i, _i, _i]),
+    "hvk_lp_loss_grad": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _sz, _p]),
+    "hvk_lp_decision": (_i, [_p, _i, _i, _p, _p, _i, _p, _p]),
+    "hvk_lp_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _f, _p, _p, _p]),
 }
 
 _lib = None
-ABI_VERSION = 18  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
+ABI_VERSION = 19  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
 
 
 def load():

@@ -1866,3 +1866,158 @@ def ss_predict_tree(x, centroids, counts, tier_base, child_ptr, child_idx):
     call("hvk_ss_predict_tree", ptr(x), B, D, ptr(centroids), ptr(counts), n_tiers, _ss_tier_base(tier_base),
          ptr(child_ptr), ptr(child_idx), ptr(pred), stream())
     return pred
+
+
+# --------------------------------------------------------------------------- linear probe
+_LP_WORKSPACE = {}  # device -> uint8 buffer of hvk_lp_loss_grad (one row chunk of residuals, dW slabs)
+
+
+def _lp_rows(x, what="features"):
+    """x as f32 [B, D] with unit column stride, and its row stride (a row slice or a padded
+    buffer is read in place)."""
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError(f"{what} must be [B, D] with D >= 1, got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{what} must be float32, got {x.dtype}")
+    x = x.detach()
+    B, D = x.shape
+    if B > 0 and x.stride(1) != 1:
+        x = x.contiguous()
+    ld = x.stride(0) if B > 1 else D
+    if ld < D:  # an expanded (stride 0) batch
+        x = x.contiguous()
+        ld = D
+    return x, ld
+
+
+def _lp_sums(sum_, sumsq, D):
+    for t in (sum_, sumsq):
+        if t.dtype != torch.float64 or t.shape != (D,) or not t.is_contiguous():
+            raise ValueError(f"sum and sumsq must be contiguous float64 [{D}]")
+
+
+def lp_moments(x, sum_, sumsq, count=None):
+    """hvk_lp_moments (include/hvk.h): add the rows of `x` (f32 [B, D], any row stride) to the
+    float64 column sums `sum_` / `sumsq` [D] and B to `count` (int64 [1] on the device, optional).
+    Any split of the rows into consecutive batches leaves the same bits."""
+    x, ld = _lp_rows(x)
+    B, D = x.shape
+    _lp_sums(sum_, sumsq, D)
+    if count is not None and (count.dtype != torch.int64 or count.numel() != 1 or not count.is_cuda):
+        raise ValueError("count must be an int64 tensor of one element on the device")
+    if B == 0:
+        return
+    call("hvk_lp_moments", _dev_ptr(x, "features"), B, D, ld, ptr(sum_), ptr(sumsq), ptr(count), stream())
+
+
+def lp_standardize(x, sum_, sumsq, n):
+    """hvk_lp_standardize: (x - mean) * inv_std of `x` (f32 [B, D], any row stride) from the float64
+    sums of `n` rows; a column of zero variance keeps scale 1.  Returns (out f32 [B, D], mean f32
+    [D], inv_std f32 [D])."""
+    x, ld = _lp_rows(x)
+    B, D = x.shape
+    _lp_sums(sum_, sumsq, D)
+    if int(n) < 1:
+        raise ValueError(f"the sums hold n = {n} rows; fit the scaler first")
+    out = torch.empty(B, D, device=x.device, dtype=torch.float32)
+    mean = torch.empty(D, device=x.device, dtype=torch.float32)
+    inv_std = torch.empty(D, device=x.device, dtype=torch.float32)
+    call("hvk_lp_standardize", _dev_ptr(x, "features") if B else None, B, D, ld, ptr(sum_), ptr(sumsq), int(n),
+         ptr(out) if B else None, ptr(mean), ptr(inv_std), stream())
+    return out, mean, inv_std
+
+
+def _lp_dense(x, what):
+    if x.dtype != torch.float32:
+        raise ValueError(f"{what} must be float32, got {x.dtype}")
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError(f"{what} must be [rows, D] with D >= 1, got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return x
+
+
+def _lp_vec(t, what, dtype, n):
+    if t.dtype != dtype or t.shape != (n,) or not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous {dtype} [{n}], got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def lp_loss_grad(xs, labels, W, b, target, alpha, fold=None, skip_fold=-1, n_classes=None, out=None,
+                 check_labels=True):
+    """hvk_lp_loss_grad: loss and gradient of the R binary logistic problems (W f32 [R, D], b f32
+    [R]; problem r is "label == target[r]" with penalty alpha[r]) over `xs` (f32 [N, D] dense,
+    standardised) with `labels` int64 [N]; rows with fold[i] == skip_fold (`fold` uint8 [N]) are
+    left out.  Labels outside [0, n_classes) raise (n_classes: max(target) + 1 when None; a host
+    read, which `check_labels=False` -- the caller has checked -- avoids).  Returns (dW f32 [R, D],
+    db f32 [R], loss float64 [R]), written into `out` when given."""
+    xs = _lp_dense(xs, "xs")
+    W = _lp_dense(W, "W")
+    N, D = xs.shape
+    R = W.shape[0]
+    if N < 1 or R < 1 or W.shape[1] != D:
+        raise ValueError(f"xs {tuple(xs.shape)} and W {tuple(W.shape)} must be [N >= 1, D] and [R >= 1, D]")
+    if labels.dtype != torch.int64 or labels.shape != (N,) or not labels.is_contiguous():
+        raise ValueError(f"labels must be contiguous int64 [{N}], got {labels.dtype} {tuple(labels.shape)}")
+    b = _lp_vec(b, "b", torch.float32, R)
+    target = _lp_vec(target, "target", torch.int32, R)
+    alpha = _lp_vec(alpha, "alpha", torch.float32, R)
+    if fold is not None:
+        fold = _lp_vec(fold, "fold", torch.uint8, N)
+    if check_labels:
+        L = int(n_classes) if n_classes is not None else int(target.max().item()) + 1
+        lo, hi = int(labels.min().item()), int(labels.max().item())
+        if lo < 0 or hi >= L:
+            raise ValueError(f"labels outside [0, {L}): min {lo}, max {hi}")
+    if out is None:
+        out = (torch.empty(R, D, device=xs.device, dtype=torch.float32),
+               torch.empty(R, device=xs.device, dtype=torch.float32),
+               torch.empty(R, device=xs.device, dtype=torch.float64))
+    dW, db, loss = out
+    need = _lib.load().hvk_lp_loss_grad_workspace(N, D, R)
+    if need == 0:
+        raise ValueError(f"hvk_lp_loss_grad does not take N {N}, D {D}, R {R}")
+    ws = _LP_WORKSPACE.get(xs.device)
+    if ws is None or ws.numel() < need:
+        ws = _LP_WORKSPACE[xs.device] = torch.empty(max(need, 1 << 20), device=xs.device, dtype=torch.uint8)
+    call("hvk_lp_loss_grad", ptr(xs), N, D, ptr(labels), ptr(fold), int(skip_fold), ptr(W), ptr(b), ptr(target),
+         ptr(alpha), R, ptr(dW), ptr(db), ptr(loss), ptr(ws), ws.numel(), stream())
+    return dW, db, loss
+
+
+def lp_decision(xs, W, b):
+    """hvk_lp_decision: xs . W^T + b as dense f32 [B, R] (xs f32 [B, D], W f32 [R, D], b f32 [R])."""
+    xs = _lp_dense(xs, "xs")
+    W = _lp_dense(W, "W")
+    B, D = xs.shape
+    R = W.shape[0]
+    if R < 1 or W.shape[1] != D:
+        raise ValueError(f"xs {tuple(xs.shape)} and W {tuple(W.shape)} must be [B, D] and [R >= 1, D]")
+    b = _lp_vec(b, "b", torch.float32, R)
+    out = torch.empty(B, R, device=xs.device, dtype=torch.float32)
+    if B == 0:
+        return out
+    call("hvk_lp_decision", ptr(xs), B, D, ptr(W), ptr(b), R, ptr(out), stream())
+    return out
+
+
+def lp_step(W, b, Yw, Yb, dW, db, t, step, tol, gmax, converged, frozen=None):
+    """hvk_lp_step: one accelerated-gradient update, in place, of the iterate (W, b), the
+    extrapolated point (Yw, Yb) and the momentum sequence t from the gradient (dW, db) taken at
+    (Yw, Yb); writes gmax f32 [R] and converged uint8 [R]; rows with frozen[r] != 0 are untouched."""
+    W = _lp_dense(W, "W")
+    R, D = W.shape
+    if R < 1:
+        raise ValueError("W must have a row")
+    for name, m in (("Yw", Yw), ("dW", dW)):
+        if _lp_dense(m, name).shape != W.shape:
+            raise ValueError(f"{name} {tuple(m.shape)} does not fit W {tuple(W.shape)}")
+    for name, v in (("b", b), ("Yb", Yb), ("db", db), ("t", t), ("gmax", gmax)):
+        _lp_vec(v, name, torch.float32, R)
+    _lp_vec(converged, "converged", torch.uint8, R)
+    if frozen is not None:
+        _lp_vec(frozen, "frozen", torch.uint8, R)
+    if not float(step) > 0.0 or not float(tol) >= 0.0:
+        raise ValueError(f"step {step} must be > 0 and tol {tol} >= 0")
+    call("hvk_lp_step", ptr(W), ptr(b), ptr(Yw), ptr(Yb), ptr(dW), ptr(db), ptr(t), ptr(frozen), R, D, float(step),
+         float(tol), ptr(gmax), ptr(converged), stream())

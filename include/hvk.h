@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 18
+#define HVK_ABI_VERSION 19
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -624,6 +624,70 @@ int hvk_ss_predict_flat(const float* x, int B, int D, const float* centroids, co
 int hvk_ss_predict_tree(const float* x, int B, int D, const float* centroids, const long long* counts,
                         int n_tiers, const int* tier_base, const int* child_ptr, const int* child_idx,
                         int* pred, void* stream);
+
+/* ---- Linear-probe evaluation (linear_probe.py:189-234) -----------------------------------
+ * StandardScaler and a one-vs-rest logistic classifier on frozen features.  The classifier is the
+ * MINIMISER of the objective sklearn's SGDClassifier(loss="log_loss") descends stochastically,
+ *   F_c(w, b) = (1/N) sum_i log(1 + exp(-y_ic (w . x_i + b))) + (alpha / 2) ||w||^2,
+ * y_ic = +1 where label_i == c and -1 elsewhere (b unpenalised) -- not a replay of its SGD.  It
+ * is found by full-batch accelerated gradient: hvk_lp_loss_grad at the extrapolated point, then
+ * hvk_lp_step, for all R binary problems at once.  Nothing is atomic: equal inputs give
+ * bit-identical outputs.  Every entry point validates before its first launch.
+ *
+ * hvk_lp_moments: StandardScaler.partial_fit.  Adds the rows of x (f32 [B, D], row stride ld >= D)
+ * to sum / sumsq (double [D]) and B to *count (device int64, may be NULL).  A column has one
+ * writer, which adds its rows in ascending order: N rows in one call or in any split into
+ * consecutive batches leave bit-identical sums.  B == 0: no launch.  One launch. */
+int hvk_lp_moments(const float* x, int B, int D, int ld, double* sum, double* sumsq, long long* count,
+                   void* stream);
+
+/* hvk_lp_standardize: mean = sum / n and var = sumsq / n - mean^2 in float64 (population
+ * variance; var <= 0, a constant column, gives scale 1), rounded once to mean / inv_std f32 [D]
+ * (always written), and out[b][k] = (x[b][k] - mean[k]) * inv_std[k] in f32, out f32 [B, D] dense.
+ * The sum / sum-of-squares form loses about 1e-16 mean^2 / var of the variance, relative: features
+ * whose mean is 1e4 standard deviations off zero keep eight digits, which f32 outputs do not show.
+ * n >= 1.  One launch. */
+int hvk_lp_standardize(const float* x, int B, int D, int ld, const double* sum, const double* sumsq,
+                       long long n, float* out, float* mean, float* inv_std, void* stream);
+
+/* hvk_lp_loss_grad: loss and gradient of R binary problems at (W f32 [R, D], b f32 [R]) over
+ * the rows of xs (f32 [N, D] dense, standardised) with labels int64 [N].  Problem r separates
+ * label == target[r] (int [R]) from the rest with penalty alpha[r] (f32 [R]): R = 3 L holds the
+ * three grid values of every class.  fold (uint8 [N] or NULL): rows with fold[i] == skip_fold
+ * contribute nothing and are not counted, N_eff being the rows that remain.  Outputs
+ * dW[r] = sum_i r_ir xs_i / N_eff + alpha[r] W[r] (f32 [R, D]), db[r] = sum_i r_ir / N_eff (f32 [R])
+ * with r_ir = sigma(z_ir) - [label_i == target[r]], z = xs . W^T + b, and loss[r] = F_r (double
+ * [R], the terms f32, summed in float64).  sigma and log(1 + exp(.)) go through exp(-|z|): no
+ * overflow at any z.  Both products run on the f32-input MFMA (v_mfma_f32_16x16x4_f32).  The rows
+ * are taken in chunks (at most 8192 rows and 128 MB of residuals) whose [rows, R] residuals pass
+ * through `workspace` (hvk_lp_loss_grad_workspace(N, D, R) bytes, 16-byte aligned; it holds one
+ * chunk, the row splits' partial dW slabs and float64 partial sums, and grows with R and D but not
+ * with N beyond the first chunk); every partial sum is reduced in a fixed order that depends on
+ * (N, D, R) alone.  xs and W 16-byte aligned with D % 4 == 0 load 16 bytes at a time, anything
+ * else element by element.  R <= 524288.  3 launches per chunk + 1 or 2. */
+size_t hvk_lp_loss_grad_workspace(int N, int D, int R);
+int hvk_lp_loss_grad(const float* xs, int N, int D, const int64_t* labels, const unsigned char* fold,
+                     int skip_fold, const float* W, const float* b, const int* target, const float* alpha,
+                     int R, float* dW, float* db, double* loss, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/* hvk_lp_decision: out[i][r] = xs_i . W_r + b_r (out f32 [B, R] dense), the forward tile of
+ * hvk_lp_loss_grad with a store.  B == 0: no launch.  One launch. */
+int hvk_lp_decision(const float* xs, int B, int D, const float* W, const float* b, int R, float* out,
+                    void* stream);
+
+/* hvk_lp_step: one accelerated-gradient update of every problem r, a workgroup each.  (W, b) is
+ * the iterate, (Yw, Yb) the extrapolated point at which (dW, db) was taken, t f32 [R] the
+ * momentum sequence (start: W = Yw = 0, b = Yb = 0, t = 1).  With x+ = y - step g:
+ * gmax[r] = max |g_r| (over dW[r] and db[r]); if gmax[r] <= tol the problem is converged:
+ * converged[r] = 1, the iterate becomes y and nothing else moves (it stays converged).  Otherwise
+ * converged[r] = 0 and, by the gradient restart of O'Donoghue & Candes, g . (x+ - x) > 0 (the dot
+ * product in float64) resets the momentum: t = 1, y = x+; else t+ = (1 + sqrt(1 + 4 t^2)) / 2,
+ * y = x+ + (t - 1) / t+ (x+ - x).  Rows with frozen[r] != 0 (uint8 [R] or NULL: problems without a
+ * positive row) are left untouched, gmax and converged included.  One launch. */
+int hvk_lp_step(float* W, float* b, float* Yw, float* Yb, const float* dW, const float* db, float* t,
+                const unsigned char* frozen, int R, int D, float step, float tol, float* gmax,
+                unsigned char* converged, void* stream);
 
 #ifdef __cplusplus
 }
