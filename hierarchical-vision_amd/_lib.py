@@ -133,10 +133,11 @@ SIGNATURES = {
     "hvk_lp_loss_grad": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _sz, _p]),
     "hvk_lp_decision": (_i, [_p, _i, _i, _p, _p, _i, _p, _p]),
     "hvk_lp_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _f, _p, _p, _p]),
+    "hvk_resized_crop_u8": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
 }
 
 _lib = None
-ABI_VERSION = 19  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
+ABI_VERSION = 20  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
 
 
 def load():

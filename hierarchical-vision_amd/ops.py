@@ -1402,6 +1402,59 @@ def normalize_u8(x, mean, std):
     return out
 
 
+RESAMPLE_MAX_SRC, RESAMPLE_MAX_OUT, RESAMPLE_MAX_SCALE = 8192, 1024, 64  # hvk_resized_crop_u8's range
+
+
+def check_resized_crop(meta, box, out_hw, nbytes):
+    """hvk_resized_crop_u8's supported range (include/hvk.h) on the HOST copies of its tables:
+    meta int64 [B, 3] = (byte offset, H, W), box int32 [B, 9] = (i, j, h, w, vh, vw, oy, ox, flip),
+    nbytes the packed buffer's length.  Raises ValueError naming the first offending image; the
+    device tables are never read back, so nothing here synchronises."""
+    oh, ow = (int(v) for v in out_hw)
+    if not (1 <= oh <= RESAMPLE_MAX_OUT and 1 <= ow <= RESAMPLE_MAX_OUT):
+        raise ValueError(f"resized_crop_u8: output {oh}x{ow} outside 1..{RESAMPLE_MAX_OUT} per side")
+    if meta.device.type != "cpu" or box.device.type != "cpu":
+        raise ValueError("resized_crop_u8: meta and box are host tables (they are validated before the launch)")
+    if meta.dtype != torch.int64 or meta.ndim != 2 or meta.shape[1] != 3:
+        raise ValueError("resized_crop_u8: meta must be int64 [B, 3]")
+    if box.dtype != torch.int32 or box.ndim != 2 or box.shape[1] != 9 or box.shape[0] != meta.shape[0]:
+        raise ValueError("resized_crop_u8: box must be int32 [B, 9] with meta's B")
+    off, H, W = meta.unbind(1)
+    i, j, h, w, vh, vw, oy, ox, _ = box.long().unbind(1)
+    checks = (
+        ("image outside the packed buffer", (off < 0) | (H < 1) | (W < 1) | (off + 3 * H * W > nbytes)),
+        (f"source side above {RESAMPLE_MAX_SRC}", (H > RESAMPLE_MAX_SRC) | (W > RESAMPLE_MAX_SRC)),
+        ("box outside the image", (i < 0) | (j < 0) | (h < 1) | (w < 1) | (i + h > H) | (j + w > W)),
+        ("window outside the virtual image", (vh < 1) | (vw < 1) | (oy < 0) | (ox < 0) | (oy + oh > vh) | (ox + ow > vw)),
+        (f"scale above {RESAMPLE_MAX_SCALE}", (h > RESAMPLE_MAX_SCALE * vh) | (w > RESAMPLE_MAX_SCALE * vw)),
+    )
+    for what, bad in checks:
+        if bool(bad.any()):
+            b = int(bad.nonzero()[0])
+            raise ValueError(f"resized_crop_u8: {what} (image {b}: H x W = {int(H[b])} x {int(W[b])}, "
+                             f"box {box[b].tolist()}, output {oh}x{ow})")
+
+
+def resized_crop_u8(ragged, box, out_hw):
+    """Crop, bilinear-resample (PIL's 8-bit arithmetic, byte for byte), window and flip a ragged
+    batch of decoded HWC uint8 images in one call (hvk_resized_crop_u8): ragged = data.RaggedImages
+    with .data on the GPU, box a host int32 [B, 9] table (i, j, h, w, vh, vw, oy, ox, flip) ->
+    uint8 [B, 3, out_h, out_w].  The tables are validated on the host copies, then copied to the
+    device asynchronously."""
+    oh, ow = (int(v) for v in out_hw)
+    check_resized_crop(ragged.meta, box, (oh, ow), ragged.data.numel())
+    src = ragged.data
+    if src.dtype != torch.uint8 or src.ndim != 1:
+        raise TypeError("resized_crop_u8 takes a 1-D uint8 buffer")
+    B = box.shape[0]
+    out = torch.empty((B, 3, oh, ow), device=src.device, dtype=torch.uint8)
+    if B:
+        meta_d = ragged.meta.contiguous().to(src.device, non_blocking=True)
+        box_d = box.contiguous().to(src.device, non_blocking=True)
+        call("hvk_resized_crop_u8", ptr(src), ptr(meta_d), ptr(box_d), B, oh, ow, ptr(out), stream())
+    return out
+
+
 def patch_merge_gather(x, H, W):
     return PatchMergeGather.apply(x, H, W)
 

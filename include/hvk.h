@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 19
+#define HVK_ABI_VERSION 20
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -688,6 +688,32 @@ int hvk_lp_decision(const float* xs, int B, int D, const float* W, const float* 
 int hvk_lp_step(float* W, float* b, float* Yw, float* Yb, const float* dW, const float* db, float* t,
                 const unsigned char* frozen, int R, int D, float step, float tol, float* gmax,
                 unsigned char* converged, void* stream);
+
+/* ---- Device-side input transforms (data.py:114-126: torchvision on PIL, in CPU workers) ------
+ * hvk_resized_crop_u8: RandomResizedCrop + RandomHorizontalFlip, or Resize + CenterCrop, of a
+ * ragged batch of decoded images in one launch.  src is one packed buffer; meta int64 [B, 3] =
+ * (byte offset into src, H, W) of each image, stored HWC, RGB-interleaved, row-major (what
+ * np.asarray(pil_image) holds); box int32 [B, 9] = (i, j, h, w, vh, vw, oy, ox, flip); both tables
+ * on the device.  Image b: crop rows [i, i + h) and columns [j, j + w), resample the crop to a
+ * virtual vh x vw image, emit its window [oy, oy + out_h) x [ox, ox + out_w), mirrored
+ * horizontally where flip != 0, into out uint8 [B, 3, out_h, out_w].  RandomResizedCrop:
+ * vh = out_h, vw = out_w, oy = ox = 0; Resize + CenterCrop: the box is the whole image, (vh, vw)
+ * the resized size and (oy, ox) the centre-crop corner.
+ * The resampling is PIL's 8-bit bilinear path (Resample.c, PRECISION_BITS 22), so the output
+ * equals Image.crop(...).resize((vw, vh), BILINEAR) byte for byte: horizontal pass, rounded to
+ * uint8, then vertical, a pass whose sizes agree skipped.  Per axis n_in -> n_out in IEEE double
+ * without contraction: scale = n_in / n_out, fs = max(scale, 1), center = (x + 0.5) scale,
+ * xmin = max((int)(center - fs + 0.5), 0), xmax = min((int)(center + fs + 0.5), n_in), tap t of
+ * [0, xmax - xmin): w_t = max(0, 1 - |(t + xmin - center + 0.5) (1 / fs)|), ww their sum in tap
+ * order, k_t = (int)(0.5 + w_t / ww * 2^22), out = clamp((2^21 + sum_t pixel[xmin + t] k_t) >> 22)
+ * in 32-bit integers; taps clamp at the CROP's borders (crop-then-resize, not resize(box=)).
+ * Supported: source side <= 8192, output side 1..1024, h <= 64 vh and w <= 64 vw, the window
+ * inside the virtual image, the box inside the image.  The shape arguments are validated here
+ * (HVK_EINVAL, no launch); the tables are device memory, so their rows are validated by the caller
+ * on its host copies (hvamd.ops.resized_crop_u8), and a row outside the range is never
+ * dereferenced: its output image is zero-filled.  B == 0: no launch.  One launch.  ABI 20. */
+int hvk_resized_crop_u8(const uint8_t* src, const int64_t* meta, const int32_t* box, int B, int out_h,
+                        int out_w, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }
