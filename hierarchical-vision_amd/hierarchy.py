@@ -381,6 +381,17 @@ def fine_grained_predictions(output, topk=1, hierarchy_level=-1):
     return output.topk(maxk, dim=1, largest=True, sorted=True)[1]
 
 
+def crm_predictions(outputs, tree_dists):
+    """CRM decoding (Karthik et al., ICLR 2021): the class of least expected tree distance under
+    softmax(outputs), int64 [B]; a list of outputs gives its finest tier's logits, as
+    fine_grained_predictions takes them.  `tree_dists`: uint8 [L, L] on the logits' device."""
+    if isinstance(outputs, (list, tuple)):
+        outputs = outputs[-1]
+    targets = torch.zeros(outputs.shape[0], device=outputs.device, dtype=torch.int64)
+    state = torch.zeros(EvalMetrics.N_STATE, device=outputs.device, dtype=torch.float64)
+    return ops.crm_predict(outputs, targets, tree_dists, state)[0].long()
+
+
 class _SumMetric(torch.nn.Module):
     """Minimal torchmetrics-style accumulator (update / compute / reset)."""
 
@@ -484,6 +495,11 @@ class EvalMetrics(torch.nn.Module):
     and adds the per-tier top-1 accuracies.  Ties follow one rule: equal logits rank by index,
     lowest first (a stable descending sort).
 
+    decoding="crm" also scores the CRM prediction of every row (ops.crm_predict: the class of
+    least expected tree distance under the row's softmax) as "acc@1/crm" and "tree-dist/crm",
+    into the same state; it needs `tree_dists` as uint8, or a `taxonomy`, whose matrix is then
+    built once on the device (ops.tree_dist_matrix).  The default "argmax" launches nothing more.
+
     The running sums are `state`, 16 doubles on the device (layout: include/hvk.h); it is the
     module's only state_dict entry.  update() launches and returns without a host
     synchronisation, so it can be captured in a HIP graph (move the module to the device first);
@@ -491,10 +507,16 @@ class EvalMetrics(torch.nn.Module):
 
     N_STATE = 16
 
-    def __init__(self, tree_dists=None, taxonomy=None, topk=5):
+    def __init__(self, tree_dists=None, taxonomy=None, topk=5, decoding="argmax"):
         super().__init__()
         if topk < 1:
             raise ValueError(f"topk ({topk}) < 1")
+        if decoding not in ("argmax", "crm"):
+            raise ValueError(f"decoding must be 'argmax' or 'crm', got {decoding!r}")
+        if decoding == "crm" and tree_dists is None and taxonomy is None:
+            raise ValueError("decoding='crm' needs tree_dists or a taxonomy")
+        self.decoding = decoding
+        self._crm_dists = None  # the taxonomy's matrix, built on the first crm update()
         self.topk = int(topk)
         self.taxonomy = taxonomy
         self.register_buffer("state", torch.zeros(self.N_STATE, dtype=torch.float64))
@@ -504,6 +526,7 @@ class EvalMetrics(torch.nn.Module):
             paths = torch.from_numpy(np.ascontiguousarray(taxonomy.leaf_paths.astype(np.int32)))
         self.register_buffer("leaf_paths", paths, persistent=False)
         self.pred = self.rank = self.nll = self.dist = self.tier_hit = None  # the last batch's rows
+        self.crm_pred = self.crm_risk = self.crm_dist = None
 
     @property
     def has_dist(self):
@@ -533,9 +556,17 @@ class EvalMetrics(torch.nn.Module):
             kw = dict(tree_dists=self.tree_dists)
         self.pred, self.rank, self.nll, self.dist, self.tier_hit = ops.eval_metrics(
             outputs, targets, self.state, topk=self.topk, **kw)
+        if self.decoding == "crm":
+            dists = self.tree_dists
+            if dists is None:
+                if self._crm_dists is None or self._crm_dists.device != outputs.device:
+                    self._crm_dists = ops.tree_dist_matrix(self.leaf_paths)
+                dists = self._crm_dists
+            self.crm_pred, self.crm_risk, self.crm_dist = ops.crm_predict(outputs, targets, dists, self.state)
 
     def compute(self):
-        """{"acc@1", "acc@{topk}", "cross-entropy"[, "tree-dist"][, "acc@1/tier0" .. "tier6"]} as
+        """{"acc@1", "acc@{topk}", "cross-entropy"[, "tree-dist"][, "acc@1/tier0" .. "tier6"]
+        [, "acc@1/crm", "tree-dist/crm"]} as
         Python floats over every update() since reset(), summed over the ranks when
         torch.distributed is initialised."""
         state = self.state
@@ -553,6 +584,9 @@ class EvalMetrics(torch.nn.Module):
         if self.leaf_paths is not None:
             for t in range(N_TIERS):
                 out[f"acc@1/tier{t}"] = div(s[6 + t])
+        if self.decoding == "crm":
+            out["acc@1/crm"] = div(s[13])
+            out["tree-dist/crm"] = div(s[14])
         return out
 
 

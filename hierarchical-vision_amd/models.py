@@ -113,17 +113,21 @@ class Model(torch.nn.Module):
         # fused_metrics() needs to score what the dicts above score
         self._metrics_info = metrics_info
 
-    def fused_metrics(self, is_train=False):
+    def fused_metrics(self, is_train=False, decoding="argmax"):
         """A fresh hierarchy.EvalMetrics, on the parameters' device, reporting what
         get_metrics(is_train) reports (models.py:61-101) from one kernel pass per batch:
         acc@1, acc@5, cross-entropy, with tree-dist where the reference adds it (the validation
         metrics of "multitask"; every set when the config is not a training one); the "hxe"
-        variant's taxonomy also gives tree-dist and the per-tier accuracies."""
+        variant's taxonomy also gives tree-dist and the per-tier accuracies.  decoding="crm" adds
+        the CRM prediction's acc@1 and tree-dist (EvalMetrics); it is handed the DatasetInfo's
+        matrix, or else its taxonomy, also where the reference's set has no tree-dist."""
         variant, cfg_train, info = self._metrics_info or ("", True, None)
         with_dist = (variant == "multitask" and not is_train) or not cfg_train
-        m = hierarchy.EvalMetrics(
-            tree_dists=info.tree_dists if info is not None and with_dist else None,
-            taxonomy=info.taxonomy if info is not None and variant == "hxe" else None, topk=5)
+        tree_dists = info.tree_dists if info is not None and with_dist else None
+        taxonomy = info.taxonomy if info is not None and variant == "hxe" else None
+        if decoding == "crm" and info is not None and tree_dists is None and taxonomy is None:
+            tree_dists, taxonomy = (info.tree_dists, None) if info.tree_dists is not None else (None, info.taxonomy)
+        m = hierarchy.EvalMetrics(tree_dists=tree_dists, taxonomy=taxonomy, topk=5, decoding=decoding)
         p = next(self.parameters(), None)
         return m.to(p.device) if p is not None else m
 

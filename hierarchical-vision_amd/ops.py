@@ -1694,16 +1694,9 @@ def _dev_ptr(t, what):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def eval_metrics(logits, targets, state, topk=5, tree_dists=None, leaf_paths=None, target_paths=None,
-                 tier_hit=False):
-    """hvk_eval_metrics (include/hvk.h): per-row argmax, target rank, NLL and tree distance of
-    `logits` [B, L] (f32 or bf16; any row stride, so a column slice or a padded buffer is read in
-    place) against the classes `targets` ([B], or [B, T] integer labels whose last column counts,
-    read through its stride), added into `state` (float64 [16] on the device).  Tree distance
-    from `tree_dists` (uint8 or f32 [L, L]) or from `leaf_paths` (int32 [L, 7]) with
-    `target_paths` (int64 [B, 7]); `tier_hit`: also the per-tier hit bits (leaf_paths only).
-    Not differentiable, no host synchronisation.  Returns (pred, rank, nll, dist, tier_hit or
-    None), [B] each."""
+def _eval_rows(logits, targets, who):
+    """The logit rows and target column as hvk_eval_metrics and hvk_crm_predict read them:
+    (logits, B, L, ld, targets, t_stride, t_off), copies made only where a stride does not fit."""
     if not logits.is_cuda:
         raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (logits)")
     if logits.ndim != 2:
@@ -1719,7 +1712,7 @@ def eval_metrics(logits, targets, state, topk=5, tree_dists=None, leaf_paths=Non
         logits = logits.contiguous()
         ld = L
     if targets.dtype.is_floating_point or targets.dtype == torch.bool:
-        raise ValueError("eval_metrics takes integer class targets")
+        raise ValueError(f"{who} takes integer class targets")
     if targets.ndim not in (1, 2) or targets.shape[0] != B:
         raise ValueError(f"targets {tuple(targets.shape)} do not fit logits {tuple(logits.shape)}")
     if targets.dtype != torch.int64:
@@ -1735,6 +1728,20 @@ def eval_metrics(logits, targets, state, topk=5, tree_dists=None, leaf_paths=Non
         if B > 1 and targets.stride(0) < 1:
             targets = targets.contiguous()
         t_stride, t_off = (targets.stride(0) if B > 1 else 1), 0
+    return logits, B, L, ld, targets, t_stride, t_off
+
+
+def eval_metrics(logits, targets, state, topk=5, tree_dists=None, leaf_paths=None, target_paths=None,
+                 tier_hit=False):
+    """hvk_eval_metrics (include/hvk.h): per-row argmax, target rank, NLL and tree distance of
+    `logits` [B, L] (f32 or bf16; any row stride, so a column slice or a padded buffer is read in
+    place) against the classes `targets` ([B], or [B, T] integer labels whose last column counts,
+    read through its stride), added into `state` (float64 [16] on the device).  Tree distance
+    from `tree_dists` (uint8 or f32 [L, L]) or from `leaf_paths` (int32 [L, 7]) with
+    `target_paths` (int64 [B, 7]); `tier_hit`: also the per-tier hit bits (leaf_paths only).
+    Not differentiable, no host synchronisation.  Returns (pred, rank, nll, dist, tier_hit or
+    None), [B] each."""
+    logits, B, L, ld, targets, t_stride, t_off = _eval_rows(logits, targets, "eval_metrics")
     dev = logits.device
     if state.dtype != torch.float64 or state.numel() != 16 or not state.is_contiguous():
         raise ValueError("state must be a contiguous float64 tensor of 16 elements")
@@ -1761,6 +1768,46 @@ def eval_metrics(logits, targets, state, topk=5, tree_dists=None, leaf_paths=Non
          _dev_ptr(targets, "targets"), t_stride, t_off, ptr(tree_dists), dist_dtype, ptr(leaf_paths),
          ptr(target_paths), int(topk), ptr(pred), ptr(rank), ptr(nll), ptr(dist), ptr(hit), ptr(state), stream())
     return pred, rank, nll, dist, hit
+
+
+# --------------------------------------------------------------------------- CRM decoding
+def tree_dist_matrix(leaf_paths):
+    """hvk_tree_dist_matrix: the uint8 [L, L] tree distances of `leaf_paths` (int32 [L, 7] on the
+    device), hierarchy.build_tree_dist_matrix's rule in one streaming-write kernel."""
+    if not leaf_paths.is_cuda:
+        raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (leaf_paths)")
+    if leaf_paths.dtype != torch.int32 or leaf_paths.ndim != 2 or leaf_paths.shape[1] != 7 or leaf_paths.shape[0] < 1:
+        raise ValueError(f"leaf_paths must be int32 [L, 7], got {leaf_paths.dtype} {tuple(leaf_paths.shape)}")
+    L = leaf_paths.shape[0]
+    out = torch.empty(L, L, device=leaf_paths.device, dtype=torch.uint8)
+    call("hvk_tree_dist_matrix", ptr(leaf_paths.contiguous()), L, ptr(out), stream())
+    return out
+
+
+def crm_predict(logits, targets, tree_dists, state):
+    """hvk_crm_predict (include/hvk.h): pred[b] = argmin_k sum_j tree_dists[k, j] softmax(logits_b)_j,
+    the class of least expected tree distance (lowest k among equal risks), on the f32 MFMA.
+    `logits`, `targets` and `state` as eval_metrics takes them; `tree_dists` a contiguous uint8
+    [L, L].  Adds the rows with pred == target to state[13] and their tree distances to state[14].
+    Not differentiable, no host synchronisation, no allocation besides the outputs (the workspace
+    is cached per (B, L)).  Returns (pred int32, risk f32, dist int32), [B] each."""
+    logits, B, L, ld, targets, t_stride, t_off = _eval_rows(logits, targets, "crm_predict")
+    dev = logits.device
+    if state.dtype != torch.float64 or state.numel() != 16 or not state.is_contiguous():
+        raise ValueError("state must be a contiguous float64 tensor of 16 elements")
+    if tree_dists.dtype != torch.uint8 or tuple(tree_dists.shape) != (L, L) or not tree_dists.is_contiguous():
+        raise ValueError(f"tree_dists must be a contiguous uint8 [{L}, {L}], got {tree_dists.dtype} "
+                         f"{tuple(tree_dists.shape)}")
+    pred = torch.empty(B, device=dev, dtype=torch.int32)
+    risk = torch.empty(B, device=dev, dtype=torch.float32)
+    dist = torch.empty(B, device=dev, dtype=torch.int32)
+    if B == 0:
+        return pred, risk, dist
+    ws = _workspace("crm", dev, _lib.load().hvk_crm_workspace(B, L))  # f32 words: a multiple of 4 bytes
+    call("hvk_crm_predict", _dev_ptr(logits, "logits"), 1 if logits.dtype == torch.bfloat16 else 0, B, L, ld,
+         _dev_ptr(targets, "targets"), t_stride, t_off, ptr(tree_dists), ptr(pred), ptr(risk), ptr(dist),
+         ptr(state), ptr(ws), ws.numel() * 4, stream())
+    return pred, risk, dist
 
 
 # --------------------------------------------------------------------------- SimpleShot

@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 20
+#define HVK_ABI_VERSION 21
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -548,8 +548,8 @@ int hvk_hxe_soft_bwd(const float* logits, const float* soft, int B, int L, const
  * row is counted as invalid only.  -inf logits are ordinary values; NaN logits never fault (pred
  * stays in [0, L); nll is NaN as torch's is).
  * state: double [16], added to: [0] valid rows, [1] rows with rank < 1, [2] rows with rank <
- * min(topk, L), [3] sum nll, [4] sum dist, [5] invalid rows, [6..12] hits of tier 0..6, rest
- * reserved.  The summation order depends on B only and nothing is atomic: equal inputs leave
+ * min(topk, L), [3] sum nll, [4] sum dist, [5] invalid rows, [6..12] hits of tier 0..6, [13] and
+ * [14] CRM hits and distances (written by hvk_crm_predict only, 0 otherwise), [15] reserved.  The summation order depends on B only and nothing is atomic: equal inputs leave
  * bit-identical state.  Two launches on `stream`, no synchronisation or allocation (capturable).
  * B == 0 returns HVK_OK without a launch. */
 int hvk_eval_metrics(const void* logits, int logits_dtype /* 0 f32, 1 bf16 */, int B, int L, int ld,
@@ -714,6 +714,36 @@ int hvk_lp_step(float* W, float* b, float* Yw, float* Yb, const float* dW, const
  * dereferenced: its output image is zero-filled.  B == 0: no launch.  One launch.  ABI 20. */
 int hvk_resized_crop_u8(const uint8_t* src, const int64_t* meta, const int32_t* box, int B, int out_h,
                         int out_w, uint8_t* out, void* stream);
+
+/* ---- CRM decoding (Karthik et al., ICLR 2021): argmin of the expected tree distance ---------
+ * hvk_tree_dist_matrix: out uint8 [L, L], out[k, j] = the smallest lvl in 0..6 with
+ * leaf_paths[k, 6 - lvl] == leaf_paths[j, 6 - lvl], else 7 (leaf_paths int [L, 7]): the rule of
+ * hvk_eval_metrics' path mode, as one streaming-write launch.  1 <= L <= 2^20.
+ *
+ * hvk_crm_predict: with p_b = softmax(z_b) (max-shifted, f32, IEEE expf, one division per entry),
+ *   risk_b,k = sum_j tree_dists[k, j] p_b,j   (f32-input MFMA: nothing is rounded to bf16)
+ *   pred[b]  = argmin_k risk_b,k, the LOWEST k among equal risks; two equal rows of tree_dists
+ *              give bitwise-equal risks, so the lower of the two always wins
+ *   risk[b]  = that minimum
+ *   dist[b]  = tree_dists[pred[b], t_b]; -1 for a target outside [0, L), never dereferenced
+ * logits, B, L, ld, targets, t_stride, t_off: exactly as hvk_eval_metrics.  tree_dists: uint8
+ * [L, L], dense; rows are read with 16-B loads where the base and L are multiples of 16, byte by
+ * byte otherwise, and nothing outside [L, L] is read.  1 <= L <= 2^20.
+ * state: the double [16] of hvk_eval_metrics, added to: [13] valid rows with pred == t, [14] sum
+ * of dist over the valid rows; [15] stays reserved.  Invalid rows are not counted here
+ * (hvk_eval_metrics counts them in [5]).  The summation order depends on B only and nothing is
+ * atomic: equal inputs leave bit-identical outputs and state.  NaN logits never fault: the row's
+ * risks are NaN, pred is 0 and risk +inf.
+ * workspace: hvk_crm_workspace(B, L) bytes, 16-B aligned (the f32 probabilities [B, L rounded up
+ * to 32] and one (min, class) pair per row and 128-class tile); smaller or NULL: HVK_EINVAL.
+ * Three launches on `stream`, no synchronisation or allocation (capturable).  B == 0 returns
+ * HVK_OK without a launch.  ABI 21. */
+int hvk_tree_dist_matrix(const int* leaf_paths, int L, unsigned char* out, void* stream);
+size_t hvk_crm_workspace(int B, int L);
+int hvk_crm_predict(const void* logits, int logits_dtype /* 0 f32, 1 bf16 */, int B, int L, int ld,
+                    const int64_t* targets, int t_stride, int t_off, const unsigned char* tree_dists,
+                    int* pred, float* risk, int* dist, double* state, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
