@@ -137,10 +137,13 @@ SIGNATURES = {
     "hvk_tree_dist_matrix": (_i, [_p, _i, _p, _p]),
     "hvk_crm_workspace": (_sz, [_i, _i]),
     "hvk_crm_predict": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "hvk_joint_supported": (_i, [_p]),
+    "hvk_joint_decode": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                              _p, _p]),
 }
 
 _lib = None
-ABI_VERSION = 21  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
+ABI_VERSION = 22  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
 
 
 def load():

@@ -13,7 +13,9 @@
 //   and there is no atomic anywhere, so equal inputs leave bit-identical state.
 #include <math.h>
 
-#include "hvk_common.h"
+#include "eval_row.h"
+
+using namespace hvk_eval;
 
 namespace {
 
@@ -23,39 +25,6 @@ constexpr int kTiers = 7;
 constexpr int kState = 16;
 constexpr int kSums = 13;  // state entries [0, 13) are written; the rest reserved
 static_assert(kSums == 6 + kTiers && kSums <= kState, "state layout of include/hvk.h");
-
-struct RowAcc {
-  float m;   // running maximum (never NaN: a NaN compares false and is skipped here)
-  int mi;    // lowest index holding m; INT_MAX while nothing compared equal or above
-  float s;   // sum of exp(z - m) over the entries seen
-  int cnt;   // entries ranked ahead of the target
-};
-
-// exp(a - b) as a factor of a sum shifted to b >= a: an entry (or a partial maximum) of -inf
-// contributes nothing, also where b is -inf too (-inf - -inf would be NaN)
-__device__ __forceinline__ float shifted_exp(float a, float b) { return a == -INFINITY ? 0.f : expf(a - b); }
-
-// N consecutive entries x[e] = z[j0 + e]; a thread's groups arrive in ascending j
-template <int N>
-__device__ __forceinline__ RowAcc push_group(RowAcc a, const float (&x)[N], int j0, float zt, int t) {
-  float cm = x[0];
-#pragma unroll
-  for (int e = 1; e < N; ++e) cm = fmaxf(cm, x[e]);  // fmaxf drops NaNs
-  if (cm > a.m) {  // a new maximum: one rescale per group, its index found below
-    a.s *= shifted_exp(a.m, cm);
-    a.m = cm;
-    a.mi = 0x7fffffff;
-  }
-#pragma unroll
-  for (int e = 0; e < N; ++e) {
-    const int j = j0 + e;
-    a.s += shifted_exp(x[e], a.m);
-    // float compares: -0.0 and +0.0 tie; the first entry equal to the maximum keeps the index
-    if (x[e] == a.m && j < a.mi) a.mi = j;
-    a.cnt += (x[e] > zt || (x[e] == zt && j < t)) ? 1 : 0;
-  }
-  return a;
-}
 
 // One thread's share of `groups` groups of N entries, group g holding z[first + g N ...]: groups
 // tid, tid + 256, ... in ascending order, UN of them per round with every load of the round issued
@@ -77,16 +46,6 @@ __device__ __forceinline__ RowAcc sweep(RowAcc acc, int first, int groups, int t
     }
   }
   return acc;
-}
-
-// (`c ? a.mi : b.mi` on two struct members is an lvalue, a select between two ADDRESSES, which
-// sends the structs to scratch memory: the fields are copied to scalars first, here and below)
-__device__ __forceinline__ RowAcc merge(RowAcc a, RowAcc b) {
-  const float am = a.m, bm = b.m, as = a.s, bs = b.s;
-  const int ai = a.mi, bi = b.mi;
-  const float m = fmaxf(am, bm);
-  const bool take_a = am > bm || (am == bm && ai < bi);
-  return RowAcc{m, take_a ? ai : bi, as * shifted_exp(am, m) + bs * shifted_exp(bm, m), a.cnt + b.cnt};
 }
 
 struct RowArgs {
@@ -152,18 +111,7 @@ __global__ __launch_bounds__(kThreads) void eval_rows_kernel(RowArgs a) {
   RowAcc acc = a.bf16 ? sweep_row<true>(row, L, tid, zt, t) : sweep_row<false>(row, L, tid, zt, t);
 
   // wave butterfly, then one LDS exchange across the four waves
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    RowAcc w{__shfl_xor(acc.m, o), __shfl_xor(acc.mi, o), __shfl_xor(acc.s, o), __shfl_xor(acc.cnt, o)};
-    // both lanes of a pair must reach the same bits: merge in lane order (selects on scalar
-    // copies, see merge)
-    const bool up = (tid & o) != 0;
-    const float am = acc.m, as = acc.s, wm = w.m, ws = w.s;
-    const int ai = acc.mi, ac = acc.cnt, wi = w.mi, wc = w.cnt;
-    const RowAcc lo{up ? wm : am, up ? wi : ai, up ? ws : as, up ? wc : ac};
-    const RowAcc hi{up ? am : wm, up ? ai : wi, up ? as : ws, up ? ac : wc};
-    acc = merge(lo, hi);
-  }
+  acc = wave_merge(acc, tid);
   __shared__ RowAcc part[kWaves];
   if ((tid & 63) == 0) part[tid >> 6] = acc;
   __syncthreads();
@@ -249,6 +197,12 @@ __global__ __launch_bounds__(kThreads) void eval_accumulate_kernel(int B, int km
 
 }  // namespace
 
+void hvk_eval_accumulate_launch(int B, int kmax, const int* rank, const float* nll, const int* dist,
+                                const unsigned char* tier_hit, double* state, hipStream_t st) {
+  hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(kThreads), 0, st, B, kmax, rank, nll, dist, tier_hit,
+                     state);
+}
+
 extern "C" {
 
 int hvk_eval_metrics(const void* logits, int logits_dtype, int B, int L, int ld, const int64_t* targets,
@@ -281,9 +235,7 @@ int hvk_eval_metrics(const void* logits, int logits_dtype, int B, int L, int ld,
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(eval_rows_kernel, dim3(B), dim3(kThreads), 0, st, a);
   HVK_CHECK_LAUNCH("eval_rows");
-  hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(kThreads), 0, st, B, topk < L ? topk : L,
-                     static_cast<const int*>(rank), static_cast<const float*>(nll), static_cast<const int*>(dist),
-                     static_cast<const unsigned char*>(tier_hit), state);
+  hvk_eval_accumulate_launch(B, topk < L ? topk : L, rank, nll, dist, tier_hit, state, st);
   HVK_CHECK_LAUNCH("eval_accumulate");
   return HVK_OK;
 }

@@ -170,6 +170,8 @@ class Taxonomy:
         self._dev = {}
         self._soft = None
         self._soft_dev = {}
+        self._parents = None
+        self._parents_dev = {}
 
     @property
     def num_leaves(self):
@@ -201,6 +203,28 @@ class Taxonomy:
             self._dev[key] = (None if self.identity_perm else mk(self.perm), mk(self.node_start),
                               mk(self.node_end), mk(self.tier_base), mk(self.leaf_paths))
         return self._dev[key]
+
+    def parent_tables(self):
+        """(tier_off [8], parents) as numpy int32, built once: tier t is columns [tier_off[t],
+        tier_off[t + 1]) of the concatenated tier logits, and the parent (a tier t - 1 id) of
+        node n of tier t >= 1 is parents[tier_off[t] - tier_off[1] + n] (hvk_joint_decode)."""
+        if self._parents is None:
+            off = np.r_[0, np.cumsum(self.num_classes)].astype(np.int32)
+            parents = np.full(off[-1] - off[1], -1, np.int32)
+            for t in range(1, N_TIERS):
+                parents[off[t] - off[1] + self.leaf_paths[:, t]] = self.leaf_paths[:, t - 1]
+            if (parents < 0).any():
+                raise ValueError("a tier id has no leaf below it")
+            self._parents = (off, parents)
+        return self._parents
+
+    def device_parent_tables(self, device):
+        """(parents int32, leaf_paths int32 [L, 7]) of parent_tables() on `device`."""
+        key = str(device)
+        if key not in self._parents_dev:
+            mk = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+            self._parents_dev[key] = (mk(self.parent_tables()[1]), mk(self.leaf_paths.astype(np.int32)))
+        return self._parents_dev[key]
 
     def soft_tables(self):
         """The node-slot tables of the soft-target HXE kernels (numpy int32, built once).
@@ -392,6 +416,33 @@ def crm_predictions(outputs, tree_dists):
     return ops.crm_predict(outputs, targets, tree_dists, state)[0].long()
 
 
+def _joint_decode(outputs, taxonomy, weights, want_scores):
+    if not isinstance(outputs, (list, tuple)) or len(outputs) != N_TIERS:
+        raise ValueError(f"joint decoding takes the list of {N_TIERS} tier logits")
+    if [o.shape[1] for o in outputs] != list(taxonomy.num_classes):
+        raise ValueError(f"tier logits {[o.shape[1] for o in outputs]} do not fit the taxonomy "
+                         f"{list(taxonomy.num_classes)}")
+    dev = outputs[-1].device
+    parents, paths = taxonomy.device_parent_tables(dev)
+    targets = torch.zeros(outputs[-1].shape[0], device=dev, dtype=torch.int64)
+    state = torch.zeros(EvalMetrics.N_STATE, device=dev, dtype=torch.float64)
+    return ops.joint_decode(outputs, targets, parents, paths, weights, state, want_scores=want_scores)
+
+
+def joint_scores(outputs, taxonomy, weights=None):
+    """Joint path decoding of the 7 tier logits (ops.joint_decode, hvk_joint_decode): (scores f32
+    [B, L], lse f32 [B]) with log p(k) = scores[:, k] - lse = sum_t w_t log softmax(z_t)[anc_t(k)]
+    - log Z, the product of the heads' softmaxes along leaf k's path; weights None = 1 per tier."""
+    out = _joint_decode(outputs, taxonomy, weights, True)
+    return out["scores"], out["lse"]
+
+
+def joint_predictions(outputs, taxonomy, weights=None):
+    """argmax_k of joint_scores, int64 [B] (the lowest k among equal scores), without storing the
+    scores."""
+    return _joint_decode(outputs, taxonomy, weights, False)["pred"].long()
+
+
 class _SumMetric(torch.nn.Module):
     """Minimal torchmetrics-style accumulator (update / compute / reset)."""
 
@@ -500,26 +551,44 @@ class EvalMetrics(torch.nn.Module):
     into the same state; it needs `tree_dists` as uint8, or a `taxonomy`, whose matrix is then
     built once on the device (ops.tree_dist_matrix).  The default "argmax" launches nothing more.
 
+    decoding="joint" is for multitask checkpoints: besides the pass over the species head it
+    combines the 7 heads along every leaf's path (ops.joint_decode, weights `tier_weights`, None =
+    1 each) and scores that distribution into a second buffer `joint_state` (the same slots, slot
+    15 = rows whose heads' argmaxes form one path): "acc@1/joint", "acc@{topk}/joint",
+    "cross-entropy/joint", "tree-dist/joint", "acc@1/joint/tier0".."tier6", "path-consistency".
+    "joint-crm" also runs CRM on the joint scores: "acc@1/joint-crm", "tree-dist/joint-crm".  Both
+    need a `taxonomy` and list outputs of 7 tiers.
+
     The running sums are `state`, 16 doubles on the device (layout: include/hvk.h); it is the
-    module's only state_dict entry.  update() launches and returns without a host
+    module's only state_dict entry (with `joint_state` for the joint decodings).  update() launches and returns without a host
     synchronisation, so it can be captured in a HIP graph (move the module to the device first);
     compute() is the one device-to-host read."""
 
     N_STATE = 16
 
-    def __init__(self, tree_dists=None, taxonomy=None, topk=5, decoding="argmax"):
+    DECODINGS = ("argmax", "crm", "joint", "joint-crm")
+
+    def __init__(self, tree_dists=None, taxonomy=None, topk=5, decoding="argmax", tier_weights=None):
         super().__init__()
         if topk < 1:
             raise ValueError(f"topk ({topk}) < 1")
-        if decoding not in ("argmax", "crm"):
-            raise ValueError(f"decoding must be 'argmax' or 'crm', got {decoding!r}")
+        if decoding not in self.DECODINGS:
+            raise ValueError(f"decoding must be one of {self.DECODINGS}, got {decoding!r}")
         if decoding == "crm" and tree_dists is None and taxonomy is None:
             raise ValueError("decoding='crm' needs tree_dists or a taxonomy")
+        self.joint = decoding in ("joint", "joint-crm")
+        if self.joint and taxonomy is None:
+            raise ValueError(f"decoding={decoding!r} needs a taxonomy")
+        if tier_weights is not None and (not self.joint or len(tier_weights) != N_TIERS):
+            raise ValueError(f"tier_weights: {N_TIERS} weights, with a joint decoding only")
+        self.tier_weights = None if tier_weights is None else tuple(float(w) for w in tier_weights)
         self.decoding = decoding
         self._crm_dists = None  # the taxonomy's matrix, built on the first crm update()
         self.topk = int(topk)
         self.taxonomy = taxonomy
         self.register_buffer("state", torch.zeros(self.N_STATE, dtype=torch.float64))
+        if self.joint:
+            self.register_buffer("joint_state", torch.zeros(self.N_STATE, dtype=torch.float64))
         self.register_buffer("tree_dists", tree_dists, persistent=False)
         paths = None
         if taxonomy is not None:
@@ -527,6 +596,9 @@ class EvalMetrics(torch.nn.Module):
         self.register_buffer("leaf_paths", paths, persistent=False)
         self.pred = self.rank = self.nll = self.dist = self.tier_hit = None  # the last batch's rows
         self.crm_pred = self.crm_risk = self.crm_dist = None
+        self.joint_pred = self.joint_rank = self.joint_nll = self.joint_lse = self.joint_dist = None
+        self.joint_tier_hit = self.head_pred = self.consistent = None
+        self.joint_crm_pred = self.joint_crm_risk = self.joint_crm_dist = None
 
     @property
     def has_dist(self):
@@ -534,9 +606,22 @@ class EvalMetrics(torch.nn.Module):
 
     def reset(self):
         self.state.zero_()
+        if self.joint:
+            self.joint_state.zero_()
+
+    def _crm_matrix(self):
+        """The uint8 [L, L] matrix CRM reads: the one given, else the taxonomy's, built once."""
+        if self.tree_dists is not None:
+            return self.tree_dists
+        if self._crm_dists is None or self._crm_dists.device != self.leaf_paths.device:
+            self._crm_dists = ops.tree_dist_matrix(self.leaf_paths)
+        return self._crm_dists
 
     @torch.no_grad()
     def update(self, outputs, targets):
+        tiers = outputs
+        if self.joint and (not isinstance(outputs, (list, tuple)) or len(outputs) != N_TIERS):
+            raise ValueError(f"decoding={self.decoding!r} takes the list of {N_TIERS} tier logits")
         if isinstance(outputs, (list, tuple)):
             outputs = outputs[-1]  # the finest tier's logits, as FineGrainedAccuracy scores
         if targets.dtype.is_floating_point:
@@ -557,23 +642,34 @@ class EvalMetrics(torch.nn.Module):
         self.pred, self.rank, self.nll, self.dist, self.tier_hit = ops.eval_metrics(
             outputs, targets, self.state, topk=self.topk, **kw)
         if self.decoding == "crm":
-            dists = self.tree_dists
-            if dists is None:
-                if self._crm_dists is None or self._crm_dists.device != outputs.device:
-                    self._crm_dists = ops.tree_dist_matrix(self.leaf_paths)
-                dists = self._crm_dists
-            self.crm_pred, self.crm_risk, self.crm_dist = ops.crm_predict(outputs, targets, dists, self.state)
+            self.crm_pred, self.crm_risk, self.crm_dist = ops.crm_predict(outputs, targets, self._crm_matrix(),
+                                                                          self.state)
+        if self.joint:
+            parents, _ = self.taxonomy.device_parent_tables(outputs.device)
+            crm = self.decoding == "joint-crm"
+            B, L = outputs.shape
+            ws = ops._workspace("joint", outputs.device, 4 * B * L).view(B, L) if crm else None
+            out = ops.joint_decode(tiers, targets, parents, self.leaf_paths, self.tier_weights, self.joint_state,
+                                   topk=self.topk, want_scores=crm, scores_out=ws)
+            self.joint_pred, self.joint_rank, self.joint_nll, self.joint_lse = (out[k] for k in
+                                                                               ("pred", "rank", "nll", "lse"))
+            self.joint_dist, self.joint_tier_hit, self.head_pred, self.consistent = (
+                out[k] for k in ("dist", "tier_hit", "head_pred", "consistent"))
+            if crm:
+                self.joint_crm_pred, self.joint_crm_risk, self.joint_crm_dist = ops.crm_predict(
+                    out["scores"], targets, self._crm_matrix(), self.joint_state)
 
     def compute(self):
         """{"acc@1", "acc@{topk}", "cross-entropy"[, "tree-dist"][, "acc@1/tier0" .. "tier6"]
-        [, "acc@1/crm", "tree-dist/crm"]} as
+        [, "acc@1/crm", "tree-dist/crm"][, the "/joint" keys and "path-consistency"]} as
         Python floats over every update() since reset(), summed over the ranks when
         torch.distributed is initialised."""
-        state = self.state
+        state = torch.cat([self.state, self.joint_state]) if self.joint else self.state
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             state = state.clone()
             torch.distributed.all_reduce(state, op=torch.distributed.ReduceOp.SUM)
         s = state.tolist()  # the one device-to-host read
+        s, j = s[:self.N_STATE], s[self.N_STATE:]
         if s[5] != 0:
             raise ValueError(f"{int(s[5])} target(s) outside [0, num_classes) were passed to update()")
         n = s[0]
@@ -587,6 +683,14 @@ class EvalMetrics(torch.nn.Module):
         if self.decoding == "crm":
             out["acc@1/crm"] = div(s[13])
             out["tree-dist/crm"] = div(s[14])
+        if self.joint:
+            out.update({"acc@1/joint": div(j[1]), f"acc@{self.topk}/joint": div(j[2]), "cross-entropy/joint": div(j[3]),
+                        "tree-dist/joint": div(j[4]), "path-consistency": div(j[15])})
+            for t in range(N_TIERS):
+                out[f"acc@1/joint/tier{t}"] = div(j[6 + t])
+            if self.decoding == "joint-crm":
+                out["acc@1/joint-crm"] = div(j[13])
+                out["tree-dist/joint-crm"] = div(j[14])
         return out
 
 

@@ -120,13 +120,17 @@ class Model(torch.nn.Module):
         metrics of "multitask"; every set when the config is not a training one); the "hxe"
         variant's taxonomy also gives tree-dist and the per-tier accuracies.  decoding="crm" adds
         the CRM prediction's acc@1 and tree-dist (EvalMetrics); it is handed the DatasetInfo's
-        matrix, or else its taxonomy, also where the reference's set has no tree-dist."""
+        matrix, or else its taxonomy, also where the reference's set has no tree-dist.
+        decoding="joint" / "joint-crm" (the "multitask" variant's list outputs) is handed the
+        DatasetInfo's taxonomy and adds the joint decoding's keys."""
         variant, cfg_train, info = self._metrics_info or ("", True, None)
         with_dist = (variant == "multitask" and not is_train) or not cfg_train
         tree_dists = info.tree_dists if info is not None and with_dist else None
         taxonomy = info.taxonomy if info is not None and variant == "hxe" else None
         if decoding == "crm" and info is not None and tree_dists is None and taxonomy is None:
             tree_dists, taxonomy = (info.tree_dists, None) if info.tree_dists is not None else (None, info.taxonomy)
+        if decoding in ("joint", "joint-crm") and info is not None and variant == "multitask":
+            taxonomy = info.taxonomy
         m = hierarchy.EvalMetrics(tree_dists=tree_dists, taxonomy=taxonomy, topk=5, decoding=decoding)
         p = next(self.parameters(), None)
         return m.to(p.device) if p is not None else m

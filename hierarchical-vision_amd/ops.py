@@ -1810,6 +1810,89 @@ def crm_predict(logits, targets, tree_dists, state):
     return pred, risk, dist
 
 
+# --------------------------------------------------------------------------- joint path decoding
+def _joint_rows(outputs):
+    """The seven tiers' logits as ONE [B, sum n_t] row buffer and the tier offsets: column views of
+    one buffer (ops.head_linear's outputs) are read in place, anything else is concatenated once."""
+    if not isinstance(outputs, (list, tuple)) or len(outputs) != 7:
+        raise ValueError("joint decoding takes the list of 7 tier logits")
+    if any(o.ndim != 2 or o.shape[0] != outputs[0].shape[0] or o.shape[1] < 1 for o in outputs):
+        raise ValueError(f"tier logits must be [B, n_t], got {[tuple(o.shape) for o in outputs]}")
+    if not all(o.is_cuda for o in outputs):
+        raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (outputs)")
+    outputs = [o.detach() for o in outputs]
+    off = [0]
+    for o in outputs:
+        off.append(off[-1] + o.shape[1])
+    first, B = outputs[0], outputs[0].shape[0]
+    esz = first.element_size()
+    in_place = first.dtype in (torch.float32, torch.bfloat16) and all(
+        o.dtype == first.dtype and (o.stride(1) == 1 or o.shape[1] == 1)
+        and (B <= 1 or (o.stride(0) == first.stride(0) and o.stride(0) >= off[7]))
+        and o.data_ptr() == first.data_ptr() + off[t] * esz for t, o in enumerate(outputs))
+    if in_place:
+        buf = first.as_strided((B, off[7]), (first.stride(0) if B > 1 else off[7], 1))
+    else:
+        dt = first.dtype if first.dtype in (torch.float32, torch.bfloat16) and all(
+            o.dtype == first.dtype for o in outputs) else torch.float32
+        buf = torch.cat([o.to(dt) for o in outputs], dim=1)
+    return buf, off
+
+
+def joint_supported(tier_sizes):
+    """hvk_joint_supported: whether a taxonomy of these 7 tier sizes fits hvk_joint_decode (its
+    tiers 0-5 stay in one workgroup's LDS)."""
+    off = [0]
+    for n in tier_sizes:
+        off.append(off[-1] + int(n))
+    return len(off) == 8 and bool(_lib.load().hvk_joint_supported((ctypes.c_int * 8)(*off)))
+
+
+def joint_decode(outputs, targets, parents, leaf_paths, weights, state, topk=5, want_scores=False, scores_out=None):
+    """hvk_joint_decode (include/hvk.h): the seven heads' softmaxes combined along every leaf's
+    path, s_k = sum_t w_t log softmax(z_t)[anc_t(k)] up to a row constant, from one read of the
+    logits.  `outputs`: the 7 tier logits [B, n_t] (f32 or bf16); `targets`, `state` and `topk` as
+    eval_metrics takes them (leaf ids; the state's slots 0-12 and 15 are added to); `parents`
+    (int32 [sum n_1..6]) and `leaf_paths` (int32 [L, 7]) from Taxonomy.device_parent_tables;
+    `weights`: 7 non-negative floats, None = 1 each.  `want_scores`: also the f32 [B, L] scores
+    (into `scores_out` when given).  Not differentiable, no host synchronisation.  Returns a dict of
+    per-row tensors: pred, rank, nll, lse, dist, tier_hit, head_pred [B, 7], consistent, scores."""
+    buf, off = _joint_rows(outputs)
+    buf, B, _, ld, targets, t_stride, t_off = _eval_rows(buf, targets, "joint_decode")
+    dev, L = buf.device, off[7] - off[6]
+    if state.dtype != torch.float64 or state.numel() != 16 or not state.is_contiguous():
+        raise ValueError("state must be a contiguous float64 tensor of 16 elements")
+    if parents.dtype != torch.int32 or parents.ndim != 1 or parents.numel() != off[7] - off[1]:
+        raise ValueError(f"parents must be int32 [{off[7] - off[1]}], got {parents.dtype} {tuple(parents.shape)}")
+    if leaf_paths.dtype != torch.int32 or tuple(leaf_paths.shape) != (L, 7):
+        raise ValueError(f"leaf_paths must be int32 [{L}, 7]")
+    w = [1.0] * 7 if weights is None else [float(x) for x in weights]
+    if len(w) != 7 or not all(0.0 <= x < float("inf") for x in w):
+        raise ValueError(f"weights must be 7 finite non-negative numbers, got {w}")
+    if topk < 1:
+        raise ValueError(f"topk ({topk}) < 1")
+    c_off = (ctypes.c_int * 8)(*off)
+    if not _lib.load().hvk_joint_supported(c_off):
+        raise RuntimeError(f"hvk_joint_decode does not take tier sizes {[b - a for a, b in zip(off, off[1:])]}: "
+                           "tiers 0-5 must fit one workgroup's LDS (15360 nodes)")
+    mk = lambda *shape, dtype=torch.int32: torch.empty(*shape, device=dev, dtype=dtype)  # noqa: E731
+    out = dict(pred=mk(B), rank=mk(B), nll=mk(B, dtype=torch.float32), lse=mk(B, dtype=torch.float32), dist=mk(B),
+               tier_hit=mk(B, dtype=torch.uint8), head_pred=mk(B, 7), consistent=mk(B, dtype=torch.uint8), scores=None)
+    if want_scores:
+        if scores_out is None:
+            scores_out = mk(B, L, dtype=torch.float32)
+        elif scores_out.dtype != torch.float32 or tuple(scores_out.shape) != (B, L) or not scores_out.is_contiguous():
+            raise ValueError(f"scores_out must be a contiguous float32 [{B}, {L}]")
+        out["scores"] = scores_out
+    if B == 0:
+        return out
+    call("hvk_joint_decode", _dev_ptr(buf, "outputs"), 1 if buf.dtype == torch.bfloat16 else 0, B, ld, c_off,
+         _dev_ptr(targets, "targets"), t_stride, t_off, ptr(parents), ptr(leaf_paths), (ctypes.c_float * 7)(*w),
+         int(topk), ptr(out["pred"]), ptr(out["rank"]), ptr(out["nll"]), ptr(out["lse"]), ptr(out["dist"]),
+         ptr(out["tier_hit"]), ptr(out["head_pred"]), ptr(out["consistent"]), ptr(out["scores"]), ptr(state), stream())
+    return out
+
+
 # --------------------------------------------------------------------------- SimpleShot
 _SS_WORKSPACE = {}  # device -> uint8 buffer of hvk_ss_predict_flat's partial (min, index) pairs
 

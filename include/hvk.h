@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 21
+#define HVK_ABI_VERSION 22
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -744,6 +744,49 @@ int hvk_crm_predict(const void* logits, int logits_dtype /* 0 f32, 1 bf16 */, in
                     const int64_t* targets, int t_stride, int t_off, const unsigned char* tree_dists,
                     int* pred, float* risk, int* dist, double* state, void* workspace,
                     size_t workspace_bytes, void* stream);
+
+/* ---- Joint path decoding of the seven multitask heads ------------------------------------------
+ * The heads' softmaxes combined into one leaf distribution, a product of experts along every
+ * leaf's root-to-leaf path:
+ *   log p_b(k) = sum_t w_t log softmax(z_b,t)[anc_t(k)] - log Z_b,   t = 0 (coarsest) .. 6 (leaves).
+ * logits: f32 (logits_dtype 0) or bf16 (1), B rows of row stride ld elements holding ALL tiers
+ * side by side: tier t is columns [tier_off[t], tier_off[t + 1]) (tier_off: HOST int [8],
+ * tier_off[0] = 0, strictly growing, tier_off[7] <= ld; any offsets and any ld: 16-B loads over
+ * the aligned body of a span, element loads at its ragged ends).  L = tier_off[7] - tier_off[6].
+ * parents: device int [tier_off[7] - tier_off[1]]; the tier-(t - 1) id of the parent of node n of
+ * tier t >= 1 is parents[tier_off[t] - tier_off[1] + n] (an entry outside the tier above is
+ * clamped into it, never followed).  leaf_paths: device int [L, 7].  weights: HOST float [7],
+ * finite and >= 0 (0 switches a head off).  targets, t_stride, t_off: as hvk_eval_metrics (leaf ids).
+ * One workgroup per row reads every logit once: tiers 0-5 are staged in LDS as f32, reduced to
+ * LSE_t and the head's own argmax, then turned in place, tier by tier, into the prefix
+ *   c_t[n] = w_t (z_t[n] - LSE_t) + c_(t-1)[parent_t[n]];
+ * one sweep over the leaves forms s_k = fma(w_6, z_6[k], c_5[parent_6[k]]).  The row constant
+ * w_6 LSE_6 is NOT subtracted: it moves no argmax or rank and cancels in s_k - lse.  Per row b:
+ *   scores[b, k] = s_k (f32 [B, L] dense, or NULL: not stored); softmax(scores[b]) is p_b
+ *   lse[b]       = log sum_k exp(s_k), so log p_b(k) = scores[b, k] - lse[b]
+ *   pred[b]      = argmax_k s_k, the lowest k among equal scores
+ *   rank[b]      = #{k : s_k > s_t, or s_k == s_t and k < t} (hvk_eval_metrics' tie rule); -1 for
+ *                  a target outside [0, L), which is never dereferenced
+ *   nll[b]       = lse[b] - s_t (NaN for an invalid target)
+ *   dist[b], tier_hit[b]: tree distance and tier-hit bits of pred[b] against the target's path
+ *                  leaf_paths[t], as hvk_eval_metrics' path mode (-1 / 0 for an invalid target)
+ *   head_pred[b, t] (int [B, 7]): every head's own argmax, lowest index first
+ *   consistent[b] (uint8): 1 when head_pred[b, t - 1] == parent of head_pred[b, t] for t = 1..6
+ * state: a double [16] with hvk_eval_metrics' slot meanings, added to: [0..12] from the joint
+ * scores (invalid rows in [5]), [15] the valid rows with consistent[b] = 1; [13], [14] untouched.
+ * The summation orders depend on the shape only and nothing is atomic: equal inputs leave
+ * bit-identical outputs and state.  NaN logits never fault.
+ * Limit: tiers 0-5 together hold at most 15360 nodes (60 KB of f32 in one workgroup's LDS; iNat21
+ * has 6327); above it hvk_joint_decode returns HVK_EUNSUPPORTED with the limit in the message and
+ * hvk_joint_supported(tier_off) returns 0 (also for malformed offsets).  L <= 2^24.
+ * Three launches on `stream`, no synchronisation or allocation (capturable).  B == 0 returns
+ * HVK_OK without a launch.  ABI 22. */
+int hvk_joint_supported(const int* tier_off);
+int hvk_joint_decode(const void* logits, int logits_dtype /* 0 f32, 1 bf16 */, int B, int ld,
+                     const int* tier_off, const int64_t* targets, int t_stride, int t_off,
+                     const int* parents, const int* leaf_paths, const float* weights, int topk, int* pred,
+                     int* rank, float* nll, float* lse, int* dist, unsigned char* tier_hit, int* head_pred,
+                     unsigned char* consistent, float* scores, double* state, void* stream);
 
 #ifdef __cplusplus
 }
