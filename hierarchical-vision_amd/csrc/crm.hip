@@ -7,7 +7,8 @@
 // * crm_probs_kernel -- one workgroup per row: max, sum of expf(z - max), then expf(z - max) / sum
 //   as f32 [B, Lk] in the workspace, Lk = L rounded up to the K chunk, the padding written as 0.
 // * crm_risk_kernel -- P . D^T on the f32-input MFMA (16x16x4), nothing rounded below f32.  A
-//   workgroup owns a 32-row x 128-class tile and sweeps all of K in 32-column chunks: the P chunk
+//   workgroup owns a 32-row x 128-class tile of its own (the byte operand: not f32_tile.h's 64 x
+//   64 tile of two f32 operands) and sweeps all of K in 32-column chunks: the P chunk
 //   (f32, from the L2-resident workspace) and the D chunk (BYTES, a quarter of the traffic and of
 //   the LDS of f32) go registers -> LDS, double-buffered, so the next chunk's global loads fly over
 //   this chunk's 32 MFMAs per wave and a chunk costs one barrier.  Lane (li, g) reads 8 bytes of
@@ -15,23 +16,20 @@
 //   bytes when the operand is formed, byte s of both feeding the s-th MFMA: A and B agree on k in
 //   every lane and every class column sees the same k order, so equal rows of D give equal bits.
 //   The [B, L] risks live in accumulators only; the tile is reduced to one (min risk, lowest
-//   class) pair per row in the workspace.
+//   class) pair per row in the workspace (take_min, eval_common.h).
 // * crm_finalize_kernel -- one workgroup: folds the pairs in ascending tile order, writes pred /
 //   risk / dist and adds hits and distances to state[13] / state[14] by a fixed butterfly.
 // No atomics anywhere: equal inputs give bit-identical outputs and state.
 #include <math.h>
 
-#include "hvk_common.h"
+#include "eval_common.h"
+
+using namespace hvk_eval;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr int kTiers = 7;
-constexpr int kNoIdx = 0x7fffffff;
 constexpr int kMaxL = 1 << 20;  // L * L bytes and every index below stay far inside 64 / 32 bits
-
-constexpr int ceil_div(int a, int b) { return a / b + (a % b != 0 ? 1 : 0); }
 
 // ---------------------------------------------------------------------------------- matrix
 __device__ __forceinline__ void load_path(const int* __restrict__ paths, int L, int k, int (&p)[kTiers]) {
@@ -78,25 +76,6 @@ constexpr int kDLd = kBK + 16;  // LDS D row stride in bytes: 8-B reads of 16 ro
 constexpr int kPU = kBM * (kBK / 4) / kThreads;  // 16-B granules of P per thread and chunk
 static_assert(kPU == 1 && kBN * (kBK / 16) == kThreads && kPLd % 8 == 4 && kDLd % 16 == 0, "tile staging");
 
-__device__ __forceinline__ float load1(const void* row, int bf16, int j) {
-  if (bf16) return __uint_as_float((uint32_t) static_cast<const hvk_bf16*>(row)[j] << 16);
-  return static_cast<const float*>(row)[j];
-}
-
-// the four waves' values combined in wave order; every thread returns the same bits
-template <typename Op>
-__device__ __forceinline__ float block_reduce(float v, float* part, int tid, Op op) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float w = __shfl_xor(v, o);
-    v = (tid & o) ? op(w, v) : op(v, w);  // the same operand order in both lanes of a pair
-  }
-  __syncthreads();  // part's readers of the previous reduction are done
-  if ((tid & 63) == 0) part[tid >> 6] = v;
-  __syncthreads();
-  return op(op(part[0], part[1]), op(part[2], part[3]));
-}
-
 __global__ __launch_bounds__(kThreads) void crm_probs_kernel(const void* logits, int bf16, int L, int ld, int Lk,
                                                             float* __restrict__ probs) {
   __shared__ float part[kWaves];
@@ -105,26 +84,19 @@ __global__ __launch_bounds__(kThreads) void crm_probs_kernel(const void* logits,
   float* p = probs + (size_t)b * Lk;
   float m = -INFINITY;
   for (int j = tid; j < L; j += kThreads) m = fmaxf(m, load1(row, bf16, HVK_BCHECK(j, L)));  // fmaxf drops NaNs
-  m = block_reduce(m, part, tid, [](float a, float c) { return fmaxf(a, c); });
+  m = block_reduce_ordered(m, part, tid, [](float a, float c) { return fmaxf(a, c); });
   float s = 0.f;
   for (int j = tid; j < L; j += kThreads) {
     const float e = expf(load1(row, bf16, j) - m);  // a NaN logit (or a row of -inf) makes the row NaN
     p[HVK_BCHECK(j, Lk)] = e;
     s += e;
   }
-  s = block_reduce(s, part, tid, [](float a, float c) { return a + c; });
+  s = block_reduce_ordered(s, part, tid, [](float a, float c) { return a + c; });
   // a thread divides the entries it wrote itself
   for (int j = tid; j < Lk; j += kThreads) p[j] = j < L ? p[j] / s : 0.f;
 }
 
 // ---------------------------------------------------------------------------------- risk
-// a lower risk wins; among equal risks the lower class (a NaN risk never compares below)
-__device__ __forceinline__ void take_min(float& m, int& mi, float v, int vi) {
-  const bool t = v < m || (v == m && vi < mi);
-  m = t ? v : m;
-  mi = t ? vi : mi;
-}
-
 // 16-B granule u of the [32, kBK] chunk of P at column k0: row m0 + u / 8, floats 4 (u % 8) ..;
 // rows past B read zero (Lk % kBK == 0: the columns are always inside the padded row)
 __device__ __forceinline__ uint4 p_tile_ld(const float* __restrict__ probs, int m0, int B, int Lk, int k0, int u) {
@@ -244,13 +216,7 @@ __global__ __launch_bounds__(kThreads) void crm_risk_kernel(const float* __restr
           bidx[m][r] = c;
         }
       }
-      // across the 16 lanes that share this row
-#pragma unroll
-      for (int o = 8; o >= 1; o >>= 1) {
-        const float v = __shfl_xor(best[m][r], o);
-        const int vi = __shfl_xor(bidx[m][r], o);
-        take_min(best[m][r], bidx[m][r], v, vi);
-      }
+      take_min16(best[m][r], bidx[m][r]);
       if (li == 0) {
         const int row = m * 16 + 4 * g + r;
         xmin[wave][row] = best[m][r];
@@ -296,12 +262,7 @@ __global__ __launch_bounds__(kThreads) void crm_finalize_kernel(const float* __r
   __shared__ double part[kWaves][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    double x = v[i];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const double y = __shfl_xor(x, o);
-      x = (tid & o) ? y + x : x + y;  // the same operand order in both lanes of a pair
-    }
+    const double x = wave_sum_ordered(v[i], tid);
     if ((tid & 63) == 0) part[tid >> 6][i] = x;
   }
   __syncthreads();

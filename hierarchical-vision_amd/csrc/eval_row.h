@@ -3,13 +3,13 @@
 #pragma once
 #include <math.h>
 
-#include "hvk_common.h"
+#include "eval_common.h"
 
 namespace hvk_eval {
 
 struct RowAcc {
   float m;   // running maximum (never NaN: a NaN compares false and is skipped here)
-  int mi;    // lowest index holding m; INT_MAX while nothing compared equal or above
+  int mi;    // lowest index holding m; kNoIdx while nothing compared equal or above
   float s;   // sum of exp(z - m) over the entries seen
   int cnt;   // entries ranked ahead of the target
 };
@@ -27,7 +27,7 @@ __device__ __forceinline__ RowAcc push_group(RowAcc a, const float (&x)[N], int 
   if (cm > a.m) {  // a new maximum: one rescale per group, its index found below
     a.s *= shifted_exp(a.m, cm);
     a.m = cm;
-    a.mi = 0x7fffffff;
+    a.mi = kNoIdx;
   }
 #pragma unroll
   for (int e = 0; e < N; ++e) {

@@ -28,8 +28,6 @@ using namespace hvk_eval;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr int kTiers = 7;
 constexpr int kCoarse = kTiers - 1;
 // f32 coarse logits a workgroup keeps in LDS: 60 KB of the 64 KB one workgroup may take, the rest
@@ -62,12 +60,6 @@ struct JointArgs {
   unsigned char* consistent;
   float* scores;  // [B, L] or null
 };
-
-template <bool BF16>
-__device__ __forceinline__ float ld1(const char* row, int j) {
-  if constexpr (BF16) return __uint_as_float((uint32_t) reinterpret_cast<const hvk_bf16*>(row)[j] << 16);
-  return reinterpret_cast<const float*>(row)[j];
-}
 
 template <bool BF16>
 __device__ __forceinline__ void unpack(const uint4& w, float (&x)[BF16 ? 8 : 4]) {
@@ -109,8 +101,8 @@ __global__ __launch_bounds__(kThreads) void joint_rows_kernel(JointArgs a) {
   float* c = lds + ((4 - (head & 3)) & 3);  // c[head + v N] is 16-B aligned in LDS
   {
     const int done = head + nv * N;
-    for (int j = tid; j < head; j += kThreads) c[j] = ld1<BF16>(row, HVK_BCHECK(j, nc));
-    for (int j = done + tid; j < nc; j += kThreads) c[j] = ld1<BF16>(row, HVK_BCHECK(j, nc));
+    for (int j = tid; j < head; j += kThreads) c[j] = load1(row, BF16, HVK_BCHECK(j, nc));
+    for (int j = done + tid; j < nc; j += kThreads) c[j] = load1(row, BF16, HVK_BCHECK(j, nc));
     const char* body = row + (size_t)head * esz;
     constexpr int UN = 4;  // every load of a round issued before the first value is used
     for (int v0 = tid; v0 < nv; v0 += kThreads * UN) {
@@ -139,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void joint_rows_kernel(JointArgs a) {
   for (int t = 0; t < kCoarse; ++t) {
     const float* z = c + a.off[t];
     const int n = a.off[t + 1] - a.off[t];
-    RowAcc acc{-INFINITY, 0x7fffffff, 0.f, 0};
+    RowAcc acc{-INFINITY, kNoIdx, 0.f, 0};
     for (int j = tid; j < n; j += kThreads) {
       const float x[1] = {z[j]};
       acc = push_group<1>(acc, x, j, nanf_, -1);
@@ -185,15 +177,15 @@ __global__ __launch_bounds__(kThreads) void joint_rows_kernel(JointArgs a) {
   const bool valid = t64 >= 0 && t64 < L;
   const int t = valid ? (int)t64 : -1;
   // the target's score by the sweep's own expression: bitwise the s_k met at k == t
-  const float st = valid ? __builtin_fmaf(w6, ld1<BF16>(lrow, HVK_BCHECK(t, L)), c5[parent_in(par[HVK_BCHECK(t, L)], n5)])
+  const float st = valid ? __builtin_fmaf(w6, load1(lrow, BF16, HVK_BCHECK(t, L)), c5[parent_in(par[HVK_BCHECK(t, L)], n5)])
                          : nanf_;
   float* srow = SCORES ? a.scores + (size_t)b * L : nullptr;
 
-  RowAcc acc{-INFINITY, 0x7fffffff, 0.f, 0};  // the joint scores
-  RowAcc sp{-INFINITY, 0x7fffffff, 0.f, 0};   // the species head's own maximum (s, cnt unused)
+  RowAcc acc{-INFINITY, kNoIdx, 0.f, 0};  // the joint scores
+  RowAcc sp{-INFINITY, kNoIdx, 0.f, 0};   // the species head's own maximum (s, cnt unused)
   split_span<BF16>(lrow, L, head, nv);
   const auto one = [&](int k) {
-    const float z = ld1<BF16>(lrow, HVK_BCHECK(k, L));
+    const float z = load1(lrow, BF16, HVK_BCHECK(k, L));
     const float s[1] = {__builtin_fmaf(w6, z, c5[parent_in(par[k], n5)])};
     if constexpr (SCORES) srow[k] = s[0];
     acc = push_group<1>(acc, s, k, st, t);
@@ -233,7 +225,7 @@ __global__ __launch_bounds__(kThreads) void joint_rows_kernel(JointArgs a) {
         float cm = z[0];
 #pragma unroll
         for (int e = 1; e < N; ++e) cm = fmaxf(cm, z[e]);
-        if (cm > sp.m) sp.m = cm, sp.mi = 0x7fffffff;
+        if (cm > sp.m) sp.m = cm, sp.mi = kNoIdx;
 #pragma unroll
         for (int e = 0; e < N; ++e)
           if (z[e] == sp.m && k0 + e < sp.mi) sp.mi = k0 + e;

@@ -6,15 +6,15 @@
 //   batch's rows to float64 sum / sum of squares in ascending row order (one writer per column, so
 //   any split into consecutive batches leaves the same bits); (x - mean) * inv_std in f32.
 // * lp_fwd_kernel -- z = xs . W^T + b on the f32-input MFMA (16x16x4), the 64 x 64 tile of
-//   ss_flat_kernel (simpleshot.hip): a workgroup holds 64 rows against a range of 64-class tiles.
+//   f32_tile.h: a workgroup holds 64 rows against a range of 64-class tiles.
 //   MODE 0 turns the scores into residuals sigma(z) - [label == target] that go to a workspace of
 //   one row chunk ([chunk rows, R padded to 64]; masked rows, padded rows and padded classes are
 //   zero) and into per-(row tile, class) float64 sums of the loss terms and residuals; MODE 1 stores
 //   the scores (decision_function).
 // * lp_bwd_kernel -- partial dW = residual^T . xs of one row chunk: a workgroup owns a 64-class x
 //   64-column tile and a fixed range of the chunk's rows, both operands staged transposed in LDS so
-//   that the MFMA loop is the forward's.  Row splits write their own slab; chunk after chunk adds
-//   to it in stream order (one writer per cell).
+//   that the MFMA step is the forward's (mfma_chunk, f32_tile.h).  Row splits write their own
+//   slab; chunk after chunk adds to it in stream order (one writer per cell).
 // * lp_chunk_reduce_kernel / lp_count_kernel / lp_finish_kernel -- the row tiles' float64 partials
 //   in ascending order, the rows outside the held-out fold, and dW = (sum of slabs in ascending
 //   order) / N_eff + alpha W, db, loss.
@@ -23,14 +23,12 @@
 // No atomics anywhere: equal inputs give bit-identical outputs.
 #include <math.h>
 
-#include "hvk_common.h"
+#include "f32_tile.h"
+
+using namespace hvk_eval;
+using namespace hvk_f32_tile;
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-
-constexpr int ceil_div(int a, int b) { return a / b + (a % b != 0 ? 1 : 0); }
 
 // ---------------------------------------------------------------------------------- scaler
 __global__ __launch_bounds__(64) void lp_moments_kernel(const float* __restrict__ x, int B, int D, int ld,
@@ -67,32 +65,6 @@ __global__ __launch_bounds__(kThreads) void lp_standardize_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------- forward tile
-constexpr int kBM = 64;       // rows per workgroup: 16 per wave
-constexpr int kBN = 64;       // classes per tile: 4 accumulators per wave
-constexpr int kBK = 32;       // contraction elements per LDS stage
-constexpr int kLd = kBK + 4;  // LDS row stride in floats (simpleshot.hip)
-constexpr int kGr = kBK / 4;  // 16-B granules per tile row
-constexpr int kU = kBM * kGr / kThreads;
-static_assert(kBM == kBN && kBM * kGr % kThreads == 0 && kBK % 16 == 0 && kLd % 8 == 4, "tile staging");
-
-// four consecutive floats at (r, k) of a dense [rows, D] matrix; past the rows or the columns: 0.
-// vec: D % 4 == 0 and a 16-byte aligned base, so the four are one aligned granule.
-__device__ __forceinline__ uint4 lp_ld(const float* base, int r, int rows, int k, int D, int vec) {
-  uint4 v = make_uint4(0, 0, 0, 0);
-  if (r >= rows || k >= D) return v;
-  const float* p = base + (size_t)HVK_BCHECK(r, rows) * D + k;
-  if (vec) return hvk_ld16(p);
-  v.x = __float_as_uint(p[0]);
-  if (k + 1 < D) v.y = __float_as_uint(p[1]);
-  if (k + 2 < D) v.z = __float_as_uint(p[2]);
-  if (k + 3 < D) v.w = __float_as_uint(p[3]);
-  return v;
-}
-
-__device__ __forceinline__ uint4 lp_tile_ld(const float* base, int r0, int rows, int k0, int D, int vec, int g) {
-  return lp_ld(base, r0 + g / kGr, rows, k0 + 4 * (g % kGr), D, vec);
-}
-
 struct FwdArgs {
   const float* xs;   // [N, D]
   const float* W;    // [R, D]
@@ -121,11 +93,9 @@ __global__ __launch_bounds__(kThreads) void lp_fwd_kernel(FwdArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
   const int m0 = (MODE == 0 ? a.n0 : 0) + blockIdx.x * kBM, split = blockIdx.y;
-  const int D = a.D;
   const int tiles = ceil_div(a.R, kBN);
   const int t_lo = split * a.tiles_per_split;
   const int t_hi = t_lo + a.tiles_per_split < tiles ? t_lo + a.tiles_per_split : tiles;
-  const int chunks = ceil_div(D, kBK);
 
   // this lane's four rows: 16 wave + 4 g + r
   int64_t lab[4] = {0, 0, 0, 0};
@@ -144,47 +114,8 @@ __global__ __launch_bounds__(kThreads) void lp_fwd_kernel(FwdArgs a) {
   for (int t = t_lo; t < t_hi; ++t) {
     const int c0 = t * kBN;
     hvk_f32x4 acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = hvk_f32x4{0.f, 0.f, 0.f, 0.f};
-    uint4 xr[kU], cr[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      xr[u] = lp_tile_ld(a.xs, m0, a.N, 0, D, a.vec, tid + u * kThreads);
-      cr[u] = lp_tile_ld(a.W, c0, a.R, 0, D, a.vec, tid + u * kThreads);
-    }
-    for (int ch = 0; ch < chunks; ++ch) {
-      __syncthreads();  // the previous chunk's readers are done
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int gi = tid + u * kThreads;
-        *reinterpret_cast<uint4*>(&xs[(gi / kGr) * kLd + 4 * (gi % kGr)]) = xr[u];
-        *reinterpret_cast<uint4*>(&cs[(gi / kGr) * kLd + 4 * (gi % kGr)]) = cr[u];
-      }
-      __syncthreads();
-      if (ch + 1 < chunks) {
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-          xr[u] = lp_tile_ld(a.xs, m0, a.N, (ch + 1) * kBK, D, a.vec, tid + u * kThreads);
-          cr[u] = lp_tile_ld(a.W, c0, a.R, (ch + 1) * kBK, D, a.vec, tid + u * kThreads);
-        }
-      }
-      // lane group g holds columns 4g .. 4g + 3 of both operands and feeds element s to the s-th
-      // MFMA: A and B agree on k in every lane (simpleshot.hip)
-#pragma unroll
-      for (int kk = 0; kk < kBK; kk += 16) {
-        const hvk_f32x4 av = *reinterpret_cast<const hvk_f32x4*>(&xs[(wave * 16 + li) * kLd + kk + 4 * g]);
-        hvk_f32x4 bq[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          bq[j] = *reinterpret_cast<const hvk_f32x4*>(&cs[(j * 16 + li) * kLd + kk + 4 * g]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bq[j][s], acc[j], 0, 0, 0);
-      }
-    }
-    hvk_settle(acc[0], acc[1], acc[2], acc[3]);
-    // D lane l: row 4 (l >> 4) + r, column l & 15 of each 16-class block j
+    sweep(a.xs, m0, a.N, a.W, c0, a.R, a.D, a.vec, xs, cs, tid, acc);
+    // acc[j][r]: row 4 g + r of the wave's 16 against class 16 j + li
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int c = c0 + j * 16 + li;
@@ -259,8 +190,7 @@ __global__ __launch_bounds__(kThreads) void lp_count_kernel(const unsigned char*
   const int tid = threadIdx.x;
   long long n = 0;
   for (int i = tid; i < N; i += kThreads) n += (int)fold[i] != skip_fold ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o);
+  n = wave_sum_ordered(n, tid);
   if ((tid & 63) == 0) part[tid >> 6] = n;
   __syncthreads();
   if (tid == 0) *n_eff = part[0] + part[1] + part[2] + part[3];
@@ -292,7 +222,7 @@ __global__ __launch_bounds__(kThreads) void lp_bwd_kernel(const float* __restric
     for (int u = 0; u < kV; ++u) {
       const int gi = tid + u * kThreads, row = gi / kG, col = 4 * (gi % kG);
       rr[u] = hvk_ld16(res + (size_t)(k_lo + row) * Rp + c0 + col);
-      xr[u] = lp_ld(xs, n0 + k_lo + row, N, d0 + col, D, vec);
+      xr[u] = ld4(xs, n0 + k_lo + row, N, d0 + col, D, vec);
     }
   }
   for (int k = k_lo; k < k_hi; k += kBK) {
@@ -315,24 +245,14 @@ __global__ __launch_bounds__(kThreads) void lp_bwd_kernel(const float* __restric
       for (int u = 0; u < kV; ++u) {
         const int gi = tid + u * kThreads, row = gi / kG, col = 4 * (gi % kG);
         rr[u] = hvk_ld16(res + (size_t)(k + kBK + row) * Rp + c0 + col);
-        xr[u] = lp_ld(xs, n0 + k + kBK + row, N, d0 + col, D, vec);
+        xr[u] = ld4(xs, n0 + k + kBK + row, N, d0 + col, D, vec);
       }
     }
-#pragma unroll
-    for (int kk = 0; kk < kBK; kk += 16) {
-      const hvk_f32x4 av = *reinterpret_cast<const hvk_f32x4*>(&rt[(wave * 16 + li) * kLd + kk + 4 * g]);
-      hvk_f32x4 bq[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bq[j] = *reinterpret_cast<const hvk_f32x4*>(&xt[(j * 16 + li) * kLd + kk + 4 * g]);
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bq[j][s], acc[j], 0, 0, 0);
-    }
+    mfma_chunk(rt, xt, tid, acc);
   }
   hvk_settle(acc[0], acc[1], acc[2], acc[3]);
-  // D lane l: class 16 wave + 4 (l >> 4) + r of the tile, column 16 j + (l & 15); the slab is
-  // padded to [Rp, Dp]: no store leaves it
+  // acc[j][r]: class 16 wave + 4 g + r of the tile against column 16 j + li; the slab is padded
+  // to [Rp, Dp]: no store leaves it
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll

@@ -19,8 +19,6 @@ using namespace hvk_eval;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr int kTiers = 7;
 constexpr int kState = 16;
 constexpr int kSums = 13;  // state entries [0, 13) are written; the rest reserved
@@ -64,16 +62,11 @@ struct RowArgs {
   unsigned char* tier_hit;
 };
 
-__device__ __forceinline__ float load1(const void* row, int bf16, int j) {
-  if (bf16) return __uint_as_float((uint32_t) static_cast<const hvk_bf16*>(row)[j] << 16);
-  return static_cast<const float*>(row)[j];
-}
-
 // The whole row of one sample, the element type fixed at compile time so that the loads of a
 // round are straight-line code.
 template <bool BF16>
 __device__ __forceinline__ RowAcc sweep_row(const char* row, int L, int tid, float zt, int t) {
-  RowAcc acc{-INFINITY, 0x7fffffff, 0.f, 0};
+  RowAcc acc{-INFINITY, kNoIdx, 0.f, 0};
   constexpr int N = BF16 ? 8 : 4;  // entries per 16 B
   const auto one = [row](int j, float (&x)[1]) { x[0] = load1(row, BF16, j); };
   if (((uintptr_t)row & 15) == 0) {
@@ -178,12 +171,7 @@ __global__ __launch_bounds__(kThreads) void eval_accumulate_kernel(int B, int km
   __shared__ double part[kWaves][kSums];
 #pragma unroll
   for (int i = 0; i < kSums; ++i) {
-    double x = v[i];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const double y = __shfl_xor(x, o);
-      x = (tid & o) ? y + x : x + y;  // the same operand order in both lanes of a pair
-    }
+    const double x = wave_sum_ordered(v[i], tid);
     if ((tid & 63) == 0) part[tid >> 6][i] = x;
   }
   __syncthreads();

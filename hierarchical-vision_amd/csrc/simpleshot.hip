@@ -13,43 +13,26 @@
 //   CSR children of tier t + 1 in ascending child id, bottom-up, then f32 centroids (the float64
 //   mean rounded once) and their squared norms.
 // * ss_flat_kernel / ss_flat_reduce_kernel -- argmin_c (cnorm[c] - 2 x . c) on the f32-input MFMA
-//   (16x16x4): a workgroup holds 64 rows against a range of 64-class tiles, both staged through
-//   LDS in 32-column chunks; the scores live in accumulators only and every lane keeps a running
-//   (min, index) per row.  The class range is split over workgroups; a second kernel folds the
-//   splits' partial pairs in ascending split order.
+//   tile of f32_tile.h: a workgroup holds 64 rows against a range of 64-class tiles; the scores
+//   live in accumulators only and every lane keeps a running (min, index) per row (take_min,
+//   eval_common.h).  The class range is split over workgroups; a second kernel folds the splits'
+//   partial pairs in ascending split order.
 // * ss_tree_kernel -- one wave per sample with its row in LDS: at each tier the candidates (all
 //   tier-0 nodes, then the CSR children of the node just chosen) are scored one after another by
 //   sum_k (x_k - c_k)^2 across the wave's lanes.
 // No atomics anywhere: equal inputs give bit-identical outputs.
 #include <math.h>
 
-#include "hvk_common.h"
+#include "f32_tile.h"
+
+using namespace hvk_eval;
+using namespace hvk_f32_tile;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr int kMaxTiers = 8;
 
-// ceil(a / b) for a >= 0 without the a + b - 1 that overflows next to 2^31
-constexpr int ceil_div(int a, int b) { return a / b + (a % b != 0 ? 1 : 0); }
-
-// the same operand order in both lanes of a pair: every lane ends with the same bits
-__device__ __forceinline__ float wave_sum_ordered(float v, int lane) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float w = __shfl_xor(v, o);
-    v = (lane & o) ? w + v : v + w;
-  }
-  return v;
-}
-
 // ---------------------------------------------------------------------------------- prepare
-__device__ __forceinline__ float ss_load(const void* row, int bf16, int k) {
-  if (bf16) return __uint_as_float((uint32_t) static_cast<const hvk_bf16*>(row)[k] << 16);
-  return static_cast<const float*>(row)[k];
-}
-
 __global__ __launch_bounds__(kThreads) void ss_prepare_kernel(const void* x, int bf16, int B, int D, int ld,
                                                              int centered, int l2n, float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
@@ -60,21 +43,21 @@ __global__ __launch_bounds__(kThreads) void ss_prepare_kernel(const void* x, int
   float mean = 1.f;
   if (centered) {
     float s = 0.f;
-    for (int k = lane; k < D; k += 64) s += ss_load(row, bf16, HVK_BCHECK(k, D));
+    for (int k = lane; k < D; k += 64) s += load1(row, bf16, HVK_BCHECK(k, D));
     mean = wave_sum_ordered(s, lane) / (float)D;
   }
   float norm = 1.f;
   if (l2n) {
     float ss = 0.f;
     for (int k = lane; k < D; k += 64) {
-      float v = ss_load(row, bf16, k);
+      float v = load1(row, bf16, k);
       if (centered) v = v / mean;
       ss = __builtin_fmaf(v, v, ss);
     }
     norm = sqrtf(wave_sum_ordered(ss, lane));
   }
   for (int k = lane; k < D; k += 64) {
-    float v = ss_load(row, bf16, k);
+    float v = load1(row, bf16, k);
     if (centered) v = v / mean;
     if (l2n) v = v / norm;
     o[HVK_BCHECK(k, D)] = v;
@@ -188,30 +171,6 @@ __global__ __launch_bounds__(kThreads) void ss_centroid_kernel(const double* __r
 }
 
 // ---------------------------------------------------------------------------------- flat predict
-constexpr int kBM = 64;   // rows per workgroup: 16 per wave
-constexpr int kBN = 64;   // classes per tile: 4 accumulators per wave
-constexpr int kBK = 32;   // feature columns per LDS chunk
-constexpr int kLd = kBK + 4;  // LDS row stride in floats: rows 0..15 start in 16 distinct 4-bank groups
-constexpr int kGr = kBK / 4;  // 16-B granules per tile row
-constexpr int kU = kBM * kGr / kThreads;  // granules per thread and tile
-static_assert(kBM == kBN && kBM * kGr % kThreads == 0 && kBK % 16 == 0 && kLd % 8 == 4, "tile staging");
-constexpr int kNoIdx = 0x7fffffff;
-
-// a lower score wins; among equal scores the lower class index (NaN scores never compare below)
-__device__ __forceinline__ void take_min(float& m, int& mi, float v, int vi) {
-  const bool t = v < m || (v == m && vi < mi);
-  m = t ? v : m;
-  mi = t ? vi : mi;
-}
-
-// 16-B granule g of a [64, kBK] f32 tile: row g / kGr, columns 4 (g % kGr) ..; rows past
-// `rows` and columns past D read zero (D % 4 == 0: a granule is all inside or all outside)
-__device__ __forceinline__ uint4 ss_tile_ld(const float* base, int r0, int rows, int k0, int D, int g) {
-  const int r = r0 + g / kGr, k = k0 + 4 * (g % kGr);
-  if (r < rows && k < D) return hvk_ld16(base + (size_t)HVK_BCHECK(r, rows) * D + k);
-  return make_uint4(0, 0, 0, 0);
-}
-
 __global__ __launch_bounds__(kThreads) void ss_flat_kernel(const float* __restrict__ x, int B, int D,
                                                           const float* __restrict__ cent,
                                                           const float* __restrict__ cnorm, int L,
@@ -228,54 +187,13 @@ __global__ __launch_bounds__(kThreads) void ss_flat_kernel(const float* __restri
 
   float best[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
   int bidx[4] = {kNoIdx, kNoIdx, kNoIdx, kNoIdx};
-  const int chunks = ceil_div(D, kBK);
 
   for (int t = t_lo; t < t_hi; ++t) {
     const int c0 = t * kBN;
     hvk_f32x4 acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = hvk_f32x4{0.f, 0.f, 0.f, 0.f};
-    // chunk 0 into registers; inside the loop the next chunk's loads fly over this chunk's MFMAs
-    uint4 xr[kU], cr[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      xr[u] = ss_tile_ld(x, m0, B, 0, D, tid + u * kThreads);
-      cr[u] = ss_tile_ld(cent, c0, L, 0, D, tid + u * kThreads);
-    }
-    for (int ch = 0; ch < chunks; ++ch) {
-      __syncthreads();  // the previous chunk's readers are done
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int gi = tid + u * kThreads;
-        *reinterpret_cast<uint4*>(&xs[(gi / kGr) * kLd + 4 * (gi % kGr)]) = xr[u];
-        *reinterpret_cast<uint4*>(&cs[(gi / kGr) * kLd + 4 * (gi % kGr)]) = cr[u];
-      }
-      __syncthreads();
-      if (ch + 1 < chunks) {
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-          xr[u] = ss_tile_ld(x, m0, B, (ch + 1) * kBK, D, tid + u * kThreads);
-          cr[u] = ss_tile_ld(cent, c0, L, (ch + 1) * kBK, D, tid + u * kThreads);
-        }
-      }
-      // 16 columns per step: lane group g holds columns 4g .. 4g + 3 of both operands and feeds
-      // element s to the s-th MFMA, so A and B agree on k in every lane (the k order inside the
-      // 16 is a permutation; a dot product does not care)
-#pragma unroll
-      for (int kk = 0; kk < kBK; kk += 16) {
-        const hvk_f32x4 a = *reinterpret_cast<const hvk_f32x4*>(&xs[(wave * 16 + li) * kLd + kk + 4 * g]);
-        hvk_f32x4 bq[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          bq[j] = *reinterpret_cast<const hvk_f32x4*>(&cs[(j * 16 + li) * kLd + kk + 4 * g]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], bq[j][s], acc[j], 0, 0, 0);
-      }
-    }
-    hvk_settle(acc[0], acc[1], acc[2], acc[3]);
-    // D lane l: row 4 (l >> 4) + r, column l & 15 of each 16-class block j, ascending class order
+    // D % 4 == 0 and both bases 16-byte aligned (hvk_ss_predict_flat): whole granules
+    sweep(x, m0, B, cent, c0, L, D, 1, xs, cs, tid, acc);
+    // acc[j][r]: row 4 g + r of the wave's 16 against class 16 j + li, ascending class order
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int c = c0 + j * 16 + li;
@@ -293,14 +211,7 @@ __global__ __launch_bounds__(kThreads) void ss_flat_kernel(const float* __restri
   }
   // across the 16 lanes that share these rows
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int o = 8; o >= 1; o >>= 1) {
-      const float v = __shfl_xor(best[r], o);
-      const int vi = __shfl_xor(bidx[r], o);
-      take_min(best[r], bidx[r], v, vi);
-    }
-  }
+  for (int r = 0; r < 4; ++r) take_min16(best[r], bidx[r]);
   if (li == 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {

@@ -1694,6 +1694,40 @@ def _dev_ptr(t, what):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _row_view(x, what, dtypes, cast):
+    """A 2-D `x` as the kernels read rows in place through their stride (a row slice, a column
+    slice of a padded buffer): (x, B, D, ld), a copy made only where the stride does not fit.  A
+    dtype outside `dtypes` becomes f32 (`cast`) or is rejected."""
+    x = x.detach()
+    if x.dtype not in dtypes:
+        if not cast:
+            raise ValueError(f"{what} must be float32, got {x.dtype}")
+        x = x.float()
+    B, D = x.shape
+    if B > 0 and D > 0 and x.stride(1) != 1:
+        x = x.contiguous()
+    ld = x.stride(0) if B > 1 else D
+    if ld < D:  # an expanded (stride 0) batch
+        x = x.contiguous()
+        ld = D
+    return x, B, D, ld
+
+
+def _label_column(labels, B):
+    """Integer class labels [B], or [B, T >= 1] whose last column counts, as the kernels read them
+    through a stride: (int64 labels, t_stride, t_off), a copy made only where a stride does not
+    fit."""
+    if labels.dtype != torch.int64:
+        labels = labels.to(torch.int64)
+    if labels.ndim == 2:
+        if labels.stride(1) != 1 or (B > 1 and labels.stride(0) < labels.shape[1]):
+            labels = labels.contiguous()
+        return labels, (labels.stride(0) if B > 1 else labels.shape[1]), labels.shape[1] - 1
+    if B > 1 and labels.stride(0) < 1:
+        labels = labels.contiguous()
+    return labels, (labels.stride(0) if B > 1 else 1), 0
+
+
 def _eval_rows(logits, targets, who):
     """The logit rows and target column as hvk_eval_metrics and hvk_crm_predict read them:
     (logits, B, L, ld, targets, t_stride, t_off), copies made only where a stride does not fit."""
@@ -1701,34 +1735,14 @@ def _eval_rows(logits, targets, who):
         raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (logits)")
     if logits.ndim != 2:
         raise ValueError(f"logits must be [B, L], got {tuple(logits.shape)}")
-    logits = logits.detach()
-    if logits.dtype not in (torch.float32, torch.bfloat16):
-        logits = logits.float()
-    B, L = logits.shape
-    if B > 0 and L > 0 and logits.stride(1) != 1:
-        logits = logits.contiguous()
-    ld = logits.stride(0) if B > 1 else L
-    if ld < L:  # an expanded (stride 0) batch
-        logits = logits.contiguous()
-        ld = L
+    logits, B, L, ld = _row_view(logits, "logits", (torch.float32, torch.bfloat16), cast=True)
     if targets.dtype.is_floating_point or targets.dtype == torch.bool:
         raise ValueError(f"{who} takes integer class targets")
     if targets.ndim not in (1, 2) or targets.shape[0] != B:
         raise ValueError(f"targets {tuple(targets.shape)} do not fit logits {tuple(logits.shape)}")
-    if targets.dtype != torch.int64:
-        targets = targets.to(torch.int64)
-    if targets.ndim == 2:
-        if targets.shape[1] < 1:
-            raise ValueError("targets [B, 0]")
-        if targets.stride(1) != 1 or (B > 1 and targets.stride(0) < targets.shape[1]):
-            targets = targets.contiguous()
-        t_stride = targets.stride(0) if B > 1 else targets.shape[1]
-        t_off = targets.shape[1] - 1
-    else:
-        if B > 1 and targets.stride(0) < 1:
-            targets = targets.contiguous()
-        t_stride, t_off = (targets.stride(0) if B > 1 else 1), 0
-    return logits, B, L, ld, targets, t_stride, t_off
+    if targets.ndim == 2 and targets.shape[1] < 1:
+        raise ValueError("targets [B, 0]")
+    return (logits, B, L, ld) + _label_column(targets, B)
 
 
 def eval_metrics(logits, targets, state, topk=5, tree_dists=None, leaf_paths=None, target_paths=None,
@@ -1917,16 +1931,7 @@ def ss_prepare(features, centered=False, l2_normalized=False):
         raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (features)")
     if features.ndim != 2:
         raise ValueError(f"features must be [B, D], got {tuple(features.shape)}")
-    x = features.detach()
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        x = x.float()
-    B, D = x.shape
-    if B > 0 and D > 0 and x.stride(1) != 1:
-        x = x.contiguous()
-    ld = x.stride(0) if B > 1 else D
-    if ld < D:  # an expanded (stride 0) batch
-        x = x.contiguous()
-        ld = D
+    x, B, D, ld = _row_view(features, "features", (torch.float32, torch.bfloat16), cast=True)
     out = torch.empty(B, D, device=x.device, dtype=torch.float32)
     if B == 0 or D == 0:
         return out
@@ -1949,18 +1954,8 @@ def ss_accumulate(x, labels, sums, counts, state):
         raise ValueError("ss_accumulate takes integer class labels")
     if labels.ndim not in (1, 2) or labels.shape[0] != B or (labels.ndim == 2 and labels.shape[1] < 1):
         raise ValueError(f"labels {tuple(labels.shape)} do not fit features {tuple(x.shape)}")
-    if labels.dtype != torch.int64:
-        labels = labels.to(torch.int64)
-    if labels.ndim == 2:
-        if labels.stride(1) != 1 or (B > 1 and labels.stride(0) < labels.shape[1]):
-            labels = labels.contiguous()
-        t_stride = labels.stride(0) if B > 1 else labels.shape[1]
-        t_off = labels.shape[1] - 1
-        col = labels[:, -1]
-    else:
-        if B > 1 and labels.stride(0) < 1:
-            labels = labels.contiguous()
-        t_stride, t_off, col = (labels.stride(0) if B > 1 else 1), 0, labels
+    labels, t_stride, t_off = _label_column(labels, B)
+    col = labels[:, -1] if labels.ndim == 2 else labels  # what the stable argsort below orders
     if (sums.dtype != torch.float64 or sums.ndim != 2 or sums.shape[1] != D or not sums.is_contiguous()
             or counts.dtype != torch.int64 or counts.shape != (sums.shape[0],) or not counts.is_contiguous()):
         raise ValueError(f"sums must be contiguous float64 [L, {D}] and counts int64 [L]")
@@ -2060,16 +2055,7 @@ def _lp_rows(x, what="features"):
     buffer is read in place)."""
     if x.ndim != 2 or x.shape[1] < 1:
         raise ValueError(f"{what} must be [B, D] with D >= 1, got {tuple(x.shape)}")
-    if x.dtype != torch.float32:
-        raise ValueError(f"{what} must be float32, got {x.dtype}")
-    x = x.detach()
-    B, D = x.shape
-    if B > 0 and x.stride(1) != 1:
-        x = x.contiguous()
-    ld = x.stride(0) if B > 1 else D
-    if ld < D:  # an expanded (stride 0) batch
-        x = x.contiguous()
-        ld = D
+    x, _, _, ld = _row_view(x, what, (torch.float32,), cast=False)
     return x, ld
 
 
