@@ -120,6 +120,10 @@ SIGNATURES = {
     "hvk_hxe_bwd": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "hvk_hxe_soft_fwd": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "hvk_hxe_soft_bwd": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "hvk_soft_labels_fwd": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "hvk_soft_labels_bwd": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "hvk_soft_labels_dense_fwd": (_i, [_p, _p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "hvk_soft_labels_dense_bwd": (_i, [_p, _p, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "hvk_eval_metrics": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
     "hvk_ss_prepare": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p]),
     "hvk_ss_accumulate": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p]),
@@ -143,7 +147,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 22  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
+ABI_VERSION = 23  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
 
 
 def load():

@@ -78,10 +78,14 @@ class AlgorithmConfig:
 
 @dataclass
 class HierarchyConfig:
-    variant: str = ""  # "" | "multitask" | "hxe"
+    """soft_labels_beta: the beta of the soft-labels loss (hierarchy.SoftLabelsCrossEntropy).  The
+    reference has no such knob; the default 15.0 is this project's choice, inside the 4-30 range
+    Bertinetto et al. (CVPR 2020) sweep."""
+    variant: str = ""  # "" | "multitask" | "hxe" | "soft-labels"
     multitask_coeffs: list = field(default_factory=list)
     hxe_tree_weights: str = "uniform"  # uniform | exponential
     hxe_alpha: float = 0.1
+    soft_labels_beta: float = 15.0
 
 
 @dataclass

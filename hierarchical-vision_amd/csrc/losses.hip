@@ -12,39 +12,9 @@
 // * HXE with soft targets (LabelSmoothing on the HXE variant): the expectation of the hard
 //   loss under a leaf weight vector; every node's LSE and weight sum, bottom-up over
 //   rank-ordered node slots, one workgroup per sample; the backward is one pass over the leaves.
-#include "hvk_common.h"
+#include "taxo_row.h"
 
 namespace {
-
-constexpr int kTiers = 7;
-constexpr int kLevels = 8;  // 7 tiers + root
-
-struct Lse {
-  float m, s;
-};
-__device__ __forceinline__ Lse lse_push(Lse a, float x) {
-  if (x > a.m) {
-    a.s = a.s * __expf(a.m - x) + 1.f;
-    a.m = x;
-  } else {
-    a.s += __expf(x - a.m);
-  }
-  return a;
-}
-__device__ __forceinline__ Lse lse_merge(Lse a, Lse b) {
-  if (b.m == -INFINITY) return a;
-  if (a.m == -INFINITY) return b;
-  const float m = fmaxf(a.m, b.m);
-  return Lse{m, a.s * __expf(a.m - m) + b.s * __expf(b.m - m)};
-}
-__device__ __forceinline__ Lse wave_lse(Lse v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    Lse w{__shfl_xor(v.m, o), __shfl_xor(v.s, o)};
-    v = lse_merge(v, w);
-  }
-  return v;
-}
 
 // ----------------------------------------------------------------- multitask CE
 __global__ __launch_bounds__(256) void mt_ce_fwd_kernel(const float* __restrict__ logits, int ld,
@@ -125,21 +95,6 @@ struct HxeArgs {
   const int* nstart; const int* nend; const int* tbase; const float* coeff;
   float* row_loss; float* lse; const float* gout; float* dlogits;
 };
-
-// segment [lo, hi) in permuted positions of the target's node at level l (l = 7: all)
-__device__ __forceinline__ void level_range(const HxeArgs& a, int b, int l, int& lo, int& hi) {
-  if (l == kLevels - 1) { lo = 0; hi = a.L; return; }
-  const int tier = kTiers - 1 - l;
-  const int64_t node = a.tgt[(size_t)b * kTiers + tier];
-  const int n_nodes = tier + 1 < kTiers ? a.tbase[tier + 1] - a.tbase[tier] : a.L;
-  if (node < 0 || node >= n_nodes) {  // out-of-range target: an empty segment (NaN loss), no OOB read
-    lo = 0;
-    hi = -1;
-    return;
-  }
-  lo = a.nstart[a.tbase[tier] + (int)node];
-  hi = a.nend[a.tbase[tier] + (int)node];
-}
 
 __global__ __launch_bounds__(256) void hxe_fwd_kernel(HxeArgs a) {
   __shared__ float sm[4], ss[4];

@@ -6,7 +6,8 @@ plain Python/numpy and bit-exact with the reference.  The losses run as HIP
 kernels (ops.multitask_cross_entropy, ops.hierarchical_cross_entropy and, for
 probability targets over the leaves such as LabelSmoothing's,
 ops.hierarchical_cross_entropy_soft: the expectation of the hard HXE loss, over
-the rank-ordered node tables of Taxonomy.soft_tables()).
+the rank-ordered node tables of Taxonomy.soft_tables(); ops.soft_labels_cross_entropy and
+ops.soft_labels_cross_entropy_dense for the soft-labels loss, SoftLabelsCrossEntropy).
 """
 import collections
 import dataclasses
@@ -172,6 +173,7 @@ class Taxonomy:
         self._soft_dev = {}
         self._parents = None
         self._parents_dev = {}
+        self._norms = {}
 
     @property
     def num_leaves(self):
@@ -276,6 +278,38 @@ class Taxonomy:
             self._soft_dev[key] = (None if self.identity_perm else mk(self.perm),
                                    *(mk(a) for a in self.soft_tables()[:4]))
         return self._soft_dev[key]
+
+
+    def soft_label_norms(self, level_weights, device=None):
+        """float32 [L], by leaf id: 1 / Z_c of the soft-labels loss, Z_c = sum_l w_l (|A_l(c)| -
+        |A_{l-1}(c)|) over the nested leaf ranges A_0(c) = {c} .. A_7(c) = all leaves of c's
+        ancestors (= sum_k w[d(c, k)]).  Computed in float64 from the node sizes; cached per
+        weights and device (None: the host)."""
+        w = tuple(float(x) for x in level_weights)
+        if len(w) != N_TIERS + 1 or not all(math.isfinite(x) and x >= 0 for x in w) or w[0] <= 0:
+            raise ValueError(f"soft-label level weights must be {N_TIERS + 1} finite non-negative "
+                             f"numbers with w_0 > 0, got {w}")
+        key = (w, str(device))
+        if key not in self._norms:
+            if (w, "None") not in self._norms:
+                size = np.ones((N_TIERS + 1, self.num_leaves))  # |A_l(c)|, l = 0 the leaf itself
+                for l in range(1, N_TIERS):
+                    k = self.tier_base[N_TIERS - 1 - l] + self.leaf_paths[:, N_TIERS - 1 - l]
+                    size[l] = self.node_end[k].astype(np.float64) - self.node_start[k]
+                size[N_TIERS] = self.num_leaves
+                z = np.asarray(w) @ np.diff(size, axis=0, prepend=0.0)
+                self._norms[(w, "None")] = torch.from_numpy((1.0 / z).astype(np.float32))
+            self._norms[key] = self._norms[(w, "None")].to(device) if device is not None \
+                else self._norms[(w, "None")]
+        return self._norms[key]
+
+
+def soft_label_level_weights(beta):
+    """w_l = exp(-beta l / 7) for tree distances l = 0 .. 7, float32 [8]: the soft-labels loss's
+    target of class c is softmax_k(-beta d(c, k) / 7) (Bertinetto et al. 2020, section 3.2, with
+    the distance normalised by the tree height)."""
+    return torch.tensor([math.exp(-beta * l / N_TIERS) for l in range(N_TIERS + 1)],
+                        dtype=torch.float32)
 
 
 def hxe_level_coeffs(tree_weights="uniform", alpha=0.1):
@@ -394,6 +428,47 @@ class HierarchicalCrossEntropy(torch.nn.Module):
             targets = paths[targets]
         return ops.hierarchical_cross_entropy(logits, targets, perm, start, end, base,
                                               self.level_coeff)
+
+
+class SoftLabelsCrossEntropy(torch.nn.Module):
+    """The soft-labels loss of Bertinetto et al. (CVPR 2020, section 3.2) over leaf logits: the
+    cross-entropy against t^(c)_k = w_{d(c,k)} / Z_c, w_l = exp(-beta l / 7), d the tree distance
+    (build_tree_dist_matrix's entry) and Z_c the sum over k.  The reference has no such loss:
+    parity unpinned, pinned by a float64 restatement and closed-form tests.
+
+    forward(logits [B, n_leaves], targets [B, 7] tier ids or [B] leaf ids), or floating-point
+    targets [B, n_leaves]: non-negative leaf weights q (LabelSmoothing's smoothed leaf column),
+    the loss then being the expectation sum_c q_c L(c) of the hard loss.  `level_weights`: 8
+    weights w_0 .. w_7 in place of beta's."""
+
+    def __init__(self, taxonomy: Taxonomy, beta=15.0, level_weights=None):
+        super().__init__()
+        self.taxonomy = taxonomy
+        self.beta = float(beta)
+        w = soft_label_level_weights(beta) if level_weights is None \
+            else torch.as_tensor(level_weights, dtype=torch.float32).reshape(-1).cpu()
+        self._weights = tuple(w.tolist())  # the host copy: the key of Taxonomy.soft_label_norms
+        taxonomy.soft_label_norms(self._weights)  # validates
+        self.register_buffer("level_weight", w)
+
+    def forward(self, logits, targets):
+        if isinstance(targets, list):
+            raise NotImplementedError("the soft-labels loss takes one target tensor over the "
+                                      "leaves, not a per-tier list (that is the multitask "
+                                      "loss's form)")
+        if targets.dtype.is_floating_point:
+            if targets.shape != logits.shape:
+                raise ValueError(f"dense soft-labels targets {tuple(targets.shape)} != logits "
+                                 f"{tuple(logits.shape)}")
+            perm, rank_off, lo, hi, anc = self.taxonomy.device_soft_tables(logits.device)
+            inv_norm = self.taxonomy.soft_label_norms(self._weights, logits.device)
+            return ops.soft_labels_cross_entropy_dense(logits, targets, inv_norm, perm, rank_off,
+                                                       lo, hi, anc, self.level_weight)
+        perm, start, end, base, paths = self.taxonomy.device_tables(logits.device)
+        if targets.ndim == 1:
+            targets = paths[targets]
+        return ops.soft_labels_cross_entropy(logits, targets, perm, start, end, base,
+                                             self.level_weight)
 
 
 # --------------------------------------------------------------------------- metrics

@@ -4,8 +4,9 @@
 SwinV2 registry (the reference calls timm.create_model, models.py:19/25, which
 is absent offline; the registry gives the official SwinV2 geometries with the
 semantics of swinv2.py).  ``build_composer_model`` picks the loss by
-``config.hierarchy.variant`` in {"", "multitask", "hxe"} (models.py:105-114;
-"hxe" is implemented here, the reference raises).  ``Model`` keeps the
+``config.hierarchy.variant`` in {"", "multitask", "hxe", "soft-labels"} (models.py:105-114;
+"hxe" is implemented here, the reference raises; "soft-labels" is the soft-labels loss of the
+same paper, which the reference does not have).  ``Model`` keeps the
 ComposerModel method surface: forward(batch), loss(outputs, batch),
 get_metrics(is_train), update_metric(batch, outputs, metric).
 """
@@ -118,7 +119,7 @@ class Model(torch.nn.Module):
         get_metrics(is_train) reports (models.py:61-101) from one kernel pass per batch:
         acc@1, acc@5, cross-entropy, with tree-dist where the reference adds it (the validation
         metrics of "multitask"; every set when the config is not a training one); the "hxe"
-        variant's taxonomy also gives tree-dist and the per-tier accuracies.  decoding="crm" adds
+        and "soft-labels" variants' taxonomy also gives tree-dist and the per-tier accuracies.  decoding="crm" adds
         the CRM prediction's acc@1 and tree-dist (EvalMetrics); it is handed the DatasetInfo's
         matrix, or else its taxonomy, also where the reference's set has no tree-dist.
         decoding="joint" / "joint-crm" (the "multitask" variant's list outputs) is handed the
@@ -126,7 +127,7 @@ class Model(torch.nn.Module):
         variant, cfg_train, info = self._metrics_info or ("", True, None)
         with_dist = (variant == "multitask" and not is_train) or not cfg_train
         tree_dists = info.tree_dists if info is not None and with_dist else None
-        taxonomy = info.taxonomy if info is not None and variant == "hxe" else None
+        taxonomy = info.taxonomy if info is not None and variant in ("hxe", "soft-labels") else None
         if decoding == "crm" and info is not None and tree_dists is None and taxonomy is None:
             tree_dists, taxonomy = (info.tree_dists, None) if info.tree_dists is not None else (None, info.taxonomy)
         if decoding in ("joint", "joint-crm") and info is not None and variant == "multitask":
@@ -152,18 +153,18 @@ class Model(torch.nn.Module):
 
 
 def build_composer_model(config, dataset_info: DatasetInfo, **model_kwargs):
-    """models.py:54-118 with the "hxe" branch implemented."""
+    """models.py:54-118 with the "hxe" branch implemented and a "soft-labels" one added."""
     variant = config.hierarchy.variant
     num_classes = dataset_info.num_classes
-    if variant == "hxe":
+    if variant in ("hxe", "soft-labels"):
         tax = dataset_info.taxonomy
         if tax is None:
-            raise ValueError("hierarchy.variant=hxe needs DatasetInfo.taxonomy")
+            raise ValueError(f"hierarchy.variant={variant} needs DatasetInfo.taxonomy")
         num_classes = tax.num_leaves
     model = build_model(config, num_classes, **model_kwargs)
 
-    # metrics (models.py:61-101): the same dict keys per variant; "hxe" scores its leaf
-    # logits as the flat variant does
+    # metrics (models.py:61-101): the same dict keys per variant; "hxe" and "soft-labels" score
+    # their leaf logits as the flat variant does
     if variant == "multitask":
         def fine_grained():
             return {"cross-entropy": hierarchy.FineGrainedCrossEntropy(),
@@ -192,6 +193,9 @@ def build_composer_model(config, dataset_info: DatasetInfo, **model_kwargs):
         loss_fn = hierarchy.HierarchicalCrossEntropy(dataset_info.taxonomy,
                                                      tree_weights=config.hierarchy.hxe_tree_weights,
                                                      alpha=config.hierarchy.hxe_alpha)
+    elif variant == "soft-labels":
+        loss_fn = hierarchy.SoftLabelsCrossEntropy(dataset_info.taxonomy,
+                                                   beta=config.hierarchy.soft_labels_beta)
     elif variant == "multitask":
         loss_fn = hierarchy.MultitaskCrossEntropy(coeffs=config.hierarchy.multitask_coeffs)
     elif variant == "":

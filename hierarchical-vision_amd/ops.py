@@ -1686,6 +1686,110 @@ def hierarchical_cross_entropy_soft(logits, soft, perm, rank_off, child_lo, chil
     return (loss, node_lse, node_t) if return_nodes else loss
 
 
+class SoftLabelsCE(torch.autograd.Function):
+    """The soft-labels loss over leaf logits [B, L] for hard targets [B, 7]; see include/hvk.h
+    for the definition."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, perm, node_start, node_end, tier_base, level_weight):
+        logits = _f32(logits)
+        B, L = logits.shape
+        row_loss = torch.empty(B, device=logits.device, dtype=torch.float32)
+        lse = torch.empty(B, device=logits.device, dtype=torch.float32)
+        call("hvk_soft_labels_fwd", ptr(logits), B, L, ptr(perm), ptr(targets), ptr(node_start),
+             ptr(node_end), ptr(tier_base), ptr(level_weight), ptr(row_loss), ptr(lse), stream())
+        ctx.save_for_backward(logits, targets, perm, node_start, node_end, tier_base,
+                              level_weight, lse)
+        ctx.has_perm = perm is not None
+        return row_loss.mean()
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, targets, perm, node_start, node_end, tier_base, level_weight, lse = ctx.saved_tensors
+        B, L = logits.shape
+        dlogits = torch.empty_like(logits)
+        gout = _f32(gout.reshape(1))
+        call("hvk_soft_labels_bwd", ptr(logits), B, L, ptr(perm if ctx.has_perm else None),
+             ptr(targets), ptr(node_start), ptr(node_end), ptr(tier_base), ptr(level_weight),
+             ptr(lse), ptr(gout), ptr(dlogits), stream())
+        return dlogits, None, None, None, None, None, None
+
+
+def _check_level_weight(level_weight, logits):
+    if level_weight.numel() != 8 or level_weight.dtype != torch.float32 or level_weight.device != logits.device:
+        raise ValueError("level_weight must be 8 float32 weights on the logits' device")
+
+
+def soft_labels_cross_entropy(logits, targets, perm, node_start, node_end, tier_base, level_weight):
+    """Soft-labels loss for hard targets [B, 7] (tables: hierarchy.Taxonomy.device_tables)."""
+    if logits.ndim != 2 or targets.shape != (logits.shape[0], 7) or targets.dtype.is_floating_point:
+        raise ValueError(f"targets {tuple(targets.shape)} {targets.dtype} are not [B, 7] tier ids "
+                         f"for logits {tuple(logits.shape)}")
+    _check_level_weight(level_weight, logits)
+    return SoftLabelsCE.apply(logits, targets.to(torch.int64).contiguous(), perm, node_start,
+                              node_end, tier_base, level_weight)
+
+
+_NODE_SUM_EPOCH = {}  # node-sum workspace address -> number of forwards that have written it
+
+
+class SoftLabelsDenseCE(torch.autograd.Function):
+    """The soft-labels loss over leaf logits [B, L] with non-negative leaf weights q [B, L] as the
+    target: the expectation of the hard loss; see include/hvk.h.  The node sums [B, n_nodes + 1]
+    live in the persistent workspace of this op, so the backward belongs to the LAST forward of
+    its shape; an earlier one's raises."""
+
+    @staticmethod
+    def forward(ctx, logits, q, inv_norm, perm, rank_off, child_lo, child_hi, anc, level_weight):
+        logits = _f32(logits)
+        B, L = logits.shape
+        n_nodes = child_lo.numel() - 1
+        row_loss = torch.empty(B, device=logits.device, dtype=torch.float32)
+        stats = torch.empty((2, B), device=logits.device, dtype=torch.float32)  # lse, sum_k t_k
+        node_r = _workspace("soft_labels", logits.device, 4 * B * (n_nodes + 1)).view(B, n_nodes + 1)
+        call("hvk_soft_labels_dense_fwd", ptr(logits), ptr(q), ptr(inv_norm), B, L, ptr(perm),
+             n_nodes, ptr(rank_off), ptr(child_lo), ptr(child_hi), ptr(anc), ptr(level_weight),
+             ptr(row_loss), ptr(stats[0]), ptr(stats[1]), ptr(node_r), stream())
+        ctx.save_for_backward(logits, q, inv_norm, perm, anc, level_weight, stats)
+        ctx.has_perm = perm is not None
+        ctx.node_r = node_r
+        ctx.epoch = _NODE_SUM_EPOCH[node_r.data_ptr()] = _NODE_SUM_EPOCH.get(node_r.data_ptr(), 0) + 1
+        return row_loss.mean()
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, q, inv_norm, perm, anc, level_weight, stats = ctx.saved_tensors
+        node_r = ctx.node_r
+        if _NODE_SUM_EPOCH[node_r.data_ptr()] != ctx.epoch:
+            raise RuntimeError("soft_labels_cross_entropy_dense: a later forward of the same shape "
+                               "has overwritten this one's node sums; run its backward first")
+        B, L = logits.shape
+        dlogits = torch.empty_like(logits)
+        gout = _f32(gout.reshape(1))
+        call("hvk_soft_labels_dense_bwd", ptr(logits), ptr(q), ptr(inv_norm), B, L,
+             ptr(perm if ctx.has_perm else None), node_r.shape[1] - 1, ptr(anc), ptr(level_weight),
+             ptr(stats[0]), ptr(stats[1]), ptr(node_r), ptr(gout), ptr(dlogits), stream())
+        return dlogits, None, None, None, None, None, None, None, None
+
+
+def soft_labels_cross_entropy_dense(logits, q, inv_norm, perm, rank_off, child_lo, child_hi, anc,
+                                    level_weight, return_nodes=False):
+    """Soft-labels loss for dense targets (tables: hierarchy.Taxonomy.device_soft_tables, inv_norm:
+    Taxonomy.soft_label_norms).  return_nodes: also a copy of the forward's node sums."""
+    if q.shape != logits.shape or logits.ndim != 2:
+        raise ValueError(f"dense targets {tuple(q.shape)} != logits {tuple(logits.shape)}")
+    if anc.shape != (logits.shape[1], 6) or child_hi.numel() != child_lo.numel() \
+            or inv_norm.shape != (logits.shape[1],) or inv_norm.dtype != torch.float32:
+        raise ValueError("taxonomy tables do not fit the logits")
+    _check_level_weight(level_weight, logits)
+    loss = SoftLabelsDenseCE.apply(logits, _f32(q.detach()), inv_norm.contiguous(), perm, rank_off,
+                                   child_lo, child_hi, anc, level_weight)
+    if not return_nodes:
+        return loss
+    n = child_lo.numel()
+    return loss, _workspace("soft_labels", logits.device, 4 * logits.shape[0] * n).view(-1, n).clone()
+
+
 # --------------------------------------------------------------------------- evaluation metrics
 def _dev_ptr(t, what):
     """Device address of a tensor the kernel reads through explicit strides (a view is fine)."""

@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 22
+#define HVK_ABI_VERSION 23
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -526,6 +526,52 @@ int hvk_hxe_soft_fwd(const float* logits, const float* soft, int B, int L, const
 int hvk_hxe_soft_bwd(const float* logits, const float* soft, int B, int L, const int* perm,
                      int n_nodes, const int* anc, const float* level_coeff, const float* node_lse,
                      const float* node_t, const float* grad_out, float* dlogits, void* stream);
+
+/* ---- Soft-labels hierarchical loss (Bertinetto et al., CVPR 2020, section 3.2) ----
+ * Not in the reference; parity unpinned.  Levels l = 0 .. 7 and the tables perm, node_start,
+ * node_end, tier_base are HXE's (above): A_l(c) is the leaf range of c's ancestor at tier 6 - l,
+ * A_0(c) = {c}, A_7(c) = all leaves, and the tree distance is d(c, k) = min{l : k in A_l(c)}.
+ * level_weight f32 [8]: w_l, non-negative, finite, w_0 > 0 (the paper's exp(-beta l / 7)).  The
+ * target of class c is
+ *   t^(c)_k = w_{d(c,k)} / Z_c,   Z_c = sum_l w_l (|A_l(c)| - |A_{l-1}(c)|),  |A_{-1}| = 0.
+ * Hard targets, int64 [B, 7] tier ids (tier 6 = leaf), c = the target of sample b:
+ *   L_b = LSE(z_b) - sum_k t^(c)_k z_bk
+ *       = LSE(z_b) - (1 / Z_c) sum_l (w_l - w_{l+1}) sum_{k in A_l(c)} z_bk,         w_8 = 0
+ *   dlogits_bk = grad_out / B * (softmax(z_b)_k - w_{d(c,k)} / Z_c).
+ * Forward: row_loss f32 [B], lse f32 [B] (the row's log-sum-exp, which the backward reads).  A
+ * tier id outside its tier gives a NaN row loss (and gradient row) and no out-of-range read.
+ * No allocation, no host synchronisation; B == 0 returns HVK_OK without a launch. */
+int hvk_soft_labels_fwd(const float* logits, int B, int L, const int* perm, const int64_t* targets,
+                        const int* node_start, const int* node_end, const int* tier_base,
+                        const float* level_weight, float* row_loss, float* lse, void* stream);
+int hvk_soft_labels_bwd(const float* logits, int B, int L, const int* perm, const int64_t* targets,
+                        const int* node_start, const int* node_end, const int* tier_base,
+                        const float* level_weight, const float* lse, const float* grad_out,
+                        float* dlogits, void* stream);
+
+/* ---- Soft-labels loss with dense targets (LabelSmoothing on the soft-labels loss) -
+ * q: f32 [B, L] non-negative leaf weights (any sum; an all-zero row gives zero loss and
+ * gradient).  The loss is the expectation sum_c q_c L(c) of the hard loss above, i.e. the
+ * cross-entropy against the effective target
+ *   t_k = sum_c q_c t^(c)_k = sum_l (w_l - w_{l+1}) R(A_l(k)),   R(n) = sum_{c in n} q_c / Z_c,
+ *   L_b = LSE(z_b) sum_k t_k - sum_k t_k z_bk,
+ *   dlogits_bk = grad_out / B * (softmax(z_b)_k sum_j t_j - t_k).
+ * A one-hot q gives hvk_soft_labels_fwd's loss.  inv_norm: f32 [L], 1 / Z_c by leaf id.  Nodes are
+ * addressed by the slots of hvk_hxe_soft_fwd (rank_off, child_lo, child_hi, anc as there).
+ * Forward: row_loss, lse, tsum f32 [B] (tsum = sum_k t_k) and node_r f32 [B, n_nodes + 1], R(n) of
+ * every slot (the root last), the state the backward reads.  No atomics: values are
+ * bit-identical from run to run.  No allocation, no host synchronisation; B == 0 returns HVK_OK
+ * without a launch. */
+int hvk_soft_labels_dense_fwd(const float* logits, const float* q, const float* inv_norm, int B,
+                              int L, const int* perm, int n_nodes, const int* rank_off,
+                              const int* child_lo, const int* child_hi, const int* anc,
+                              const float* level_weight, float* row_loss, float* lse, float* tsum,
+                              float* node_r, void* stream);
+int hvk_soft_labels_dense_bwd(const float* logits, const float* q, const float* inv_norm, int B,
+                              int L, const int* perm, int n_nodes, const int* anc,
+                              const float* level_weight, const float* lse, const float* tsum,
+                              const float* node_r, const float* grad_out, float* dlogits,
+                              void* stream);
 
 /* ---- Evaluation metrics (hierarchy.py:97-180, models.py:61-101) -------------------
  * acc@1, acc@topk, cross-entropy and tree distance of a batch from one read of each logit row,
