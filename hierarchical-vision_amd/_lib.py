@@ -144,10 +144,12 @@ SIGNATURES = {
     "hvk_joint_supported": (_i, [_p]),
     "hvk_joint_decode": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                               _p, _p]),
+    "hvk_backoff_supported": (_i, [_p]),
+    "hvk_backoff_decode": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
 }
 
 _lib = None
-ABI_VERSION = 23  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
+ABI_VERSION = 24  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
 
 
 def load():

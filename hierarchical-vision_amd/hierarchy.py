@@ -171,6 +171,7 @@ class Taxonomy:
         self._dev = {}
         self._soft = None
         self._soft_dev = {}
+        self._backoff_dev = {}
         self._parents = None
         self._parents_dev = {}
         self._norms = {}
@@ -279,6 +280,17 @@ class Taxonomy:
                                    *(mk(a) for a in self.soft_tables()[:4]))
         return self._soft_dev[key]
 
+    def device_backoff_tables(self, device):
+        """(perm or None, rank_off, child_lo, child_hi, slot_node) of soft_tables() as back-off
+        decoding reads them (ops.backoff_decode): everything on `device` but rank_off, which stays
+        a host tensor -- the entry point sizes its LDS from it before the launch."""
+        key = str(device)
+        if key not in self._backoff_dev:
+            mk = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+            rank_off, child_lo, child_hi, _, slot_node = self.soft_tables()
+            self._backoff_dev[key] = (None if self.identity_perm else mk(self.perm), torch.from_numpy(rank_off),
+                                      mk(child_lo), mk(child_hi), mk(slot_node))
+        return self._backoff_dev[key]
 
     def soft_label_norms(self, level_weights, device=None):
         """float32 [L], by leaf id: 1 / Z_c of the soft-labels loss, Z_c = sum_l w_l (|A_l(c)| -
@@ -516,6 +528,104 @@ def joint_predictions(outputs, taxonomy, weights=None):
     """argmax_k of joint_scores, int64 [B] (the lowest k among equal scores), without storing the
     scores."""
     return _joint_decode(outputs, taxonomy, weights, False)["pred"].long()
+
+
+def _backoff_decode(outputs, targets, taxonomy, thresholds, state):
+    if isinstance(outputs, (list, tuple)):
+        outputs = outputs[-1]
+    if outputs.ndim != 2 or outputs.shape[1] != taxonomy.num_leaves:
+        raise ValueError(f"logits {tuple(outputs.shape)} do not fit the taxonomy's {taxonomy.num_leaves} leaves")
+    dev = outputs.device
+    return ops.backoff_decode(outputs, targets, *taxonomy.device_backoff_tables(dev),
+                              taxonomy.device_parent_tables(dev)[1], thresholds, state)
+
+
+def backoff_predictions(outputs, taxonomy, threshold=0.5):
+    """Back-off decoding (Deng et al., CVPR 2012; ops.backoff_decode, hvk_backoff_decode): descend
+    the taxonomy from the root, at every node to the child of largest mass (the softmax summed over
+    the child's leaves; the lowest node_start among equal masses), and stop at the last depth whose
+    mass is at least `threshold` (in (0, 1]).  Returns {"path": int64 [B, 7], the tier ids of the
+    greedy path and the leaf id last; "prob": f32 [B, 7], the masses along it, descending; "depth":
+    int64 [B], the entries of the path that stand: 0 answers with the root alone, 7 with a leaf}.
+    The path itself does not depend on the threshold, and its leaf need NOT be the argmax leaf: a
+    leaf may lead its row and still sit in a genus lighter than its neighbour.
+
+    A list of outputs gives its finest tier's logits, as crm_predictions takes them; any [B, L]
+    scores whose softmax is the distribution meant may be passed, so joint_scores(...)[0] backs a
+    multitask checkpoint off on its joint distribution."""
+    th = ops.backoff_thresholds((threshold,))
+    last = outputs[-1] if isinstance(outputs, (list, tuple)) else outputs
+    targets = torch.zeros(last.shape[0], device=last.device, dtype=torch.int64)
+    state = torch.zeros(BackoffMetrics.N_FIXED + BackoffMetrics.N_SUMS, device=last.device, dtype=torch.float64)
+    out = _backoff_decode(outputs, targets, taxonomy, th, state)
+    tau = torch.tensor(th[0], dtype=torch.float32, device=last.device)  # the kernel's own comparison
+    return {"path": out["path"].long(), "prob": out["prob"], "depth": (out["prob"] >= tau).sum(1)}
+
+
+class BackoffMetrics(torch.nn.Module):
+    """The operating points of back-off decoding (backoff_predictions' rule) at every threshold of
+    `thresholds` (ascending, each in (0, 1], at most 32), from one kernel pass per batch
+    (ops.backoff_decode): the hierarchical precision / recall curve of Valmadre (NeurIPS 2022), at
+    leaf depth the risk-coverage curve of selective classification.  With D the stopping depth of a
+    row, m the leading depths on which the greedy path agrees with the target's and N the rows,
+    compute() returns per threshold tau (keyed f"...@{tau:g}"):
+      backoff/depth@tau          sum D / N
+      backoff/acc@tau            rows with D <= m / N (the answer is the target or an ancestor)
+      backoff/hP@tau             sum min(D, m) / sum D
+      backoff/hR@tau             sum min(D, m) / 7 N
+      backoff/leaf-coverage@tau  rows with D = 7 / N
+      backoff/leaf-acc@tau       rows with D = 7 and m = 7 / rows with D = 7
+    (NaN where a denominator is empty).  update(outputs, targets) takes what EvalMetrics.update
+    takes: logits or a list whose finest tier counts, leaf ids or [B, T] labels whose last column
+    counts.  The running sums are `state`, 2 + 5 T doubles on the device (include/hvk.h), the
+    module's only state_dict entry; update() launches without a host synchronisation, compute() is
+    the one device-to-host read and sums over the ranks when torch.distributed is initialised."""
+
+    N_FIXED, N_SUMS = 2, 5
+
+    def __init__(self, taxonomy, thresholds=(0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99)):
+        super().__init__()
+        if taxonomy is None:
+            raise ValueError("BackoffMetrics needs a taxonomy")
+        self.thresholds = ops.backoff_thresholds(thresholds)
+        self.taxonomy = taxonomy
+        self.register_buffer("state", torch.zeros(self.N_FIXED + self.N_SUMS * len(self.thresholds),
+                                                  dtype=torch.float64))
+        self.path = self.prob = self.match = None  # the last batch's rows
+
+    def reset(self):
+        self.state.zero_()
+
+    @torch.no_grad()
+    def update(self, outputs, targets):
+        last = outputs[-1] if isinstance(outputs, (list, tuple)) else outputs
+        if targets.dtype.is_floating_point:
+            raise ValueError("BackoffMetrics takes integer class targets")
+        if self.state.device != last.device:
+            self.to(last.device)
+        out = _backoff_decode(outputs, targets, self.taxonomy, self.thresholds, self.state)
+        self.path, self.prob, self.match = out["path"], out["prob"], out["match"]
+
+    def compute(self):
+        state = self.state
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            state = state.clone()
+            torch.distributed.all_reduce(state, op=torch.distributed.ReduceOp.SUM)
+        s = state.tolist()  # the one device-to-host read
+        if s[1] != 0:
+            raise ValueError(f"{int(s[1])} target(s) outside [0, num_classes) were passed to update()")
+        n = s[0]
+        div = lambda x, d: x / d if d else float("nan")  # noqa: E731
+        out = {}
+        for j, tau in enumerate(self.thresholds):
+            depth, correct, common, at_leaf, leaf_hit = s[self.N_FIXED + self.N_SUMS * j:][:self.N_SUMS]
+            out[f"backoff/depth@{tau:g}"] = div(depth, n)
+            out[f"backoff/acc@{tau:g}"] = div(correct, n)
+            out[f"backoff/hP@{tau:g}"] = div(common, depth)
+            out[f"backoff/hR@{tau:g}"] = div(common, N_TIERS * n)
+            out[f"backoff/leaf-coverage@{tau:g}"] = div(at_leaf, n)
+            out[f"backoff/leaf-acc@{tau:g}"] = div(leaf_hit, at_leaf)
+        return out
 
 
 class _SumMetric(torch.nn.Module):

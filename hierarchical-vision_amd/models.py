@@ -136,6 +136,19 @@ class Model(torch.nn.Module):
         p = next(self.parameters(), None)
         return m.to(p.device) if p is not None else m
 
+    def backoff_metrics(self, thresholds=None):
+        """A fresh hierarchy.BackoffMetrics over the DatasetInfo's taxonomy, on the parameters'
+        device: the back-off operating points beside fused_metrics(), as
+        Trainer.eval(batches, metrics={"eval": model.fused_metrics(), "backoff": model.backoff_metrics()}).
+        `thresholds`: None for BackoffMetrics' default set."""
+        info = (self._metrics_info or ("", True, None))[2]
+        if info is None or info.taxonomy is None:
+            raise ValueError("backoff_metrics() needs a taxonomy: build the model with a DatasetInfo that has one")
+        kw = {} if thresholds is None else {"thresholds": thresholds}
+        m = hierarchy.BackoffMetrics(info.taxonomy, **kw)
+        p = next(self.parameters(), None)
+        return m.to(p.device) if p is not None else m
+
     def loss(self, outputs, batch, *args, **kwargs):
         _, targets = batch
         return self.loss_fn(outputs, targets, *args, **kwargs)

@@ -2011,6 +2011,77 @@ def joint_decode(outputs, targets, parents, leaf_paths, weights, state, topk=5, 
     return out
 
 
+# --------------------------------------------------------------------------- back-off decoding
+BACKOFF_MAX_THRESHOLDS = 32
+
+
+def backoff_thresholds(thresholds):
+    """The stopping thresholds as hvk_backoff_decode takes them: 1 to 32 floats, strictly ascending,
+    each in (0, 1] (compared as float32); returns them as a tuple."""
+    try:
+        th = tuple(float(x) for x in thresholds)
+    except TypeError:
+        raise ValueError(f"thresholds must be a sequence of numbers, got {thresholds!r}") from None
+    if not 1 <= len(th) <= BACKOFF_MAX_THRESHOLDS:
+        raise ValueError(f"{len(th)} thresholds: 1 to {BACKOFF_MAX_THRESHOLDS} are taken")
+    f32 = [ctypes.c_float(x).value for x in th]
+    if not all(0.0 < x <= 1.0 for x in f32):
+        raise ValueError(f"every threshold must lie in (0, 1], got {th}")
+    if any(b <= a for a, b in zip(f32, f32[1:])):
+        raise ValueError(f"thresholds must ascend strictly (as float32), got {th}")
+    return th
+
+
+def backoff_supported(rank_off):
+    """hvk_backoff_supported: whether the node slots of Taxonomy.soft_tables()[0] fit one
+    workgroup's LDS (15360 slots)."""
+    off = [int(x) for x in rank_off]
+    return len(off) == 8 and bool(_lib.load().hvk_backoff_supported((ctypes.c_int * 8)(*off)))
+
+
+def backoff_decode(logits, targets, perm, rank_off, child_lo, child_hi, slot_node, leaf_paths, thresholds, state):
+    """hvk_backoff_decode (include/hvk.h): the greedy walk down the taxonomy by node mass (softmax
+    summed over a node's leaves), every node's mass kept in LDS.  `logits` and `targets` as
+    eval_metrics takes them (leaf ids); `perm`, `rank_off` (host), `child_lo`, `child_hi` and
+    `slot_node` from Taxonomy.device_backoff_tables; `leaf_paths` int32 [L, 7] on the device;
+    `thresholds` as backoff_thresholds takes them; `state` float64 [2 + 5 T] on the device, added
+    to.  Not differentiable, no host synchronisation.  Returns a dict: path int32 [B, 7] (tier ids,
+    then the leaf id), prob f32 [B, 7] (the masses along the path, descending), match int32 [B] (the
+    leading depths that agree with the target's path; -1 for a target out of range)."""
+    logits, B, L, ld, targets, t_stride, t_off = _eval_rows(logits, targets, "backoff_decode")
+    dev = logits.device
+    th = backoff_thresholds(thresholds)
+    if state.dtype != torch.float64 or state.numel() != 2 + 5 * len(th) or not state.is_contiguous():
+        raise ValueError(f"state must be a contiguous float64 tensor of {2 + 5 * len(th)} elements "
+                         f"(2 + 5 per threshold)")
+    off = [int(x) for x in rank_off]
+    if len(off) != 8:
+        raise ValueError(f"rank_off must hold 8 offsets, got {len(off)}")
+    c_off = (ctypes.c_int * 8)(*off)
+    if not _lib.load().hvk_backoff_supported(c_off):
+        raise RuntimeError(f"hvk_backoff_decode does not take the node slots {off}: offsets from 0, strictly "
+                           "growing, the root last, at most 15360 slots (one workgroup's LDS)")
+    n_slots = off[7]
+    for name, t, n in (("perm", perm, L), ("child_lo", child_lo, n_slots), ("child_hi", child_hi, n_slots),
+                       ("slot_node", slot_node, n_slots - 1)):
+        if t is None and name == "perm":
+            continue
+        if t.dtype != torch.int32 or t.ndim != 1 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 [{n}], got {t.dtype} {tuple(t.shape)}")
+    if leaf_paths.dtype != torch.int32 or tuple(leaf_paths.shape) != (L, 7) or not leaf_paths.is_contiguous():
+        raise ValueError(f"leaf_paths must be a contiguous int32 [{L}, 7]")
+    out = dict(path=torch.empty(B, 7, device=dev, dtype=torch.int32),
+               prob=torch.empty(B, 7, device=dev, dtype=torch.float32),
+               match=torch.empty(B, device=dev, dtype=torch.int32))
+    if B == 0:
+        return out
+    call("hvk_backoff_decode", _dev_ptr(logits, "logits"), 1 if logits.dtype == torch.bfloat16 else 0, B, L, ld,
+         _dev_ptr(targets, "targets"), t_stride, t_off, ptr(perm), c_off, ptr(child_lo), ptr(child_hi),
+         ptr(slot_node), ptr(leaf_paths), (ctypes.c_float * len(th))(*th), len(th), ptr(out["path"]),
+         ptr(out["prob"]), ptr(out["match"]), ptr(state), stream())
+    return out
+
+
 # --------------------------------------------------------------------------- SimpleShot
 _SS_WORKSPACE = {}  # device -> uint8 buffer of hvk_ss_predict_flat's partial (min, index) pairs
 

@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 23
+#define HVK_ABI_VERSION 24
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -833,6 +833,49 @@ int hvk_joint_decode(const void* logits, int logits_dtype /* 0 f32, 1 bf16 */, i
                      const int* parents, const int* leaf_paths, const float* weights, int topk, int* pred,
                      int* rank, float* nll, float* lse, int* dist, unsigned char* tier_hit, int* head_pred,
                      unsigned char* consistent, float* scores, double* state, void* stream);
+
+/* ---- Back-off decoding: a thresholded walk down the taxonomy ------------------------------------
+ * With p = softmax(z_b) over the leaves and the node mass P(n) = sum of p over the leaves of n
+ * (depth 0 the root, P = 1; depth d = 1..7 a node of tier d - 1; depth 7 a leaf):
+ *   n_0 = the root, n_d = the child of n_(d-1) of largest mass -- among equal masses the lowest slot
+ *   (the lowest node_start), among equal leaves the lowest permuted position; q_d = P(n_d), so
+ *   1 = q_0 >= q_1 >= ... >= q_7.  The path does not depend on a threshold; the stopping depth does:
+ *   D(tau) = max{d : q_d >= tau}, and the prediction is n_D.  The greedy leaf n_7 need not be the
+ *   argmax leaf (a leaf may lead its row and still sit in a light genus).
+ * logits, logits_dtype, B, L, ld, targets, t_stride, t_off: exactly as hvk_eval_metrics (leaf ids).
+ * perm: device int [L], the leaf id at every permuted position, or NULL for the identity.
+ * rank_off: HOST int [8], child_lo / child_hi: device int [n_nodes + 1], slot_node: device int
+ * [n_nodes] -- the node-slot tables of hvk_hxe_soft_fwd (Taxonomy.soft_tables()): slot
+ * rank_off[t] + r holds the tier-t node of rank r by node_start, its tier id is slot_node[slot],
+ * its children are [child_lo, child_hi) (permuted leaf positions for tier 5, slots of the next
+ * finer tier above it), the root is slot n_nodes = rank_off[6] with the tier-0 slots as children,
+ * rank_off[7] = n_nodes + 1.  A table entry outside its children's range is clamped into it, never
+ * followed.  leaf_paths: device int [L, 7].
+ * One workgroup per row keeps one f32 mass S(n) = sum_k exp(z_k - M), M the row maximum, and the
+ * best child of every slot in LDS (8 bytes a slot, nothing per node in HBM), bottom-up over the
+ * tiers, then follows the best children from the root.  NaN logits count as -inf and never fault;
+ * a row without any mass has prob 0.  Per row b:
+ *   path[b, d - 1]  (int [B, 7]) the tier id of n_d for d = 1..6, the leaf id of n_7
+ *   prob[b, d - 1]  (f32 [B, 7]) q_d = S(n_d) / S(root); descending as computed, never above 1
+ *   match[b]        the number m of leading depths d = 1..7 with path[b, d - 1] ==
+ *                   leaf_paths[t_b, d - 1]; -1 for a target outside [0, L), never dereferenced
+ * thresholds: HOST float [n_thresholds], 1 <= n_thresholds <= 32, strictly ascending, each in
+ * (0, 1].  state: device double [2 + 5 n_thresholds], added to: [0] valid rows, [1] invalid rows
+ * (left out of every other sum), then per threshold j at [2 + 5 j ..]: sum of D, rows with D <= m
+ * (the prediction is the target or an ancestor of it), sum of min(D, m), rows with D = 7, rows with
+ * D = 7 and m = 7.  Integer counts; the summation order depends on B only and nothing is atomic:
+ * equal inputs leave bit-identical outputs and state.
+ * Limit: at most 15360 node slots (120 KB of gfx950's 160 KB of LDS; iNat21 has 6328); above it
+ * hvk_backoff_decode returns HVK_EUNSUPPORTED with the limit in the message and
+ * hvk_backoff_supported(rank_off) returns 0 (also for malformed offsets).  L <= 2^24.
+ * Two launches on `stream`, no synchronisation or allocation (capturable).  B == 0 returns HVK_OK
+ * without a launch.  ABI 24. */
+int hvk_backoff_supported(const int* rank_off);
+int hvk_backoff_decode(const void* logits, int logits_dtype /* 0 f32, 1 bf16 */, int B, int L, int ld,
+                       const int64_t* targets, int t_stride, int t_off, const int* perm, const int* rank_off,
+                       const int* child_lo, const int* child_hi, const int* slot_node, const int* leaf_paths,
+                       const float* thresholds, int n_thresholds, int* path, float* prob, int* match,
+                       double* state, void* stream);
 
 #ifdef __cplusplus
 }
