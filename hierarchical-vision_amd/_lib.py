@@ -146,10 +146,15 @@ SIGNATURES = {
                               _p, _p]),
     "hvk_backoff_supported": (_i, [_p]),
     "hvk_backoff_decode": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "hvk_cond_softmax_supported": (_i, [_p]),
+    "hvk_cond_softmax_fwd": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p]),
+    "hvk_cond_softmax_bwd": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _i, _p]),
+    "hvk_cond_softmax_decode": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p,
+                                     _p, _p]),
 }
 
 _lib = None
-ABI_VERSION = 24  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
+ABI_VERSION = 25  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
 
 
 def load():

@@ -80,12 +80,15 @@ class AlgorithmConfig:
 class HierarchyConfig:
     """soft_labels_beta: the beta of the soft-labels loss (hierarchy.SoftLabelsCrossEntropy).  The
     reference has no such knob; the default 15.0 is this project's choice, inside the 4-30 range
-    Bertinetto et al. (CVPR 2020) sweep."""
-    variant: str = ""  # "" | "multitask" | "hxe" | "soft-labels"
+    Bertinetto et al. (CVPR 2020) sweep.  "cond-softmax": the conditional softmax over the
+    MultitaskHead's node logits (hierarchy.ConditionalSoftmaxCrossEntropy), multitask_coeffs its
+    tier coefficients and cond_softmax_smoothing its label smoothing within a sibling group."""
+    variant: str = ""  # "" | "multitask" | "hxe" | "soft-labels" | "cond-softmax"
     multitask_coeffs: list = field(default_factory=list)
     hxe_tree_weights: str = "uniform"  # uniform | exponential
     hxe_alpha: float = 0.1
     soft_labels_beta: float = 15.0
+    cond_softmax_smoothing: float = 0.0
 
 
 @dataclass

@@ -174,6 +174,8 @@ class Taxonomy:
         self._backoff_dev = {}
         self._parents = None
         self._parents_dev = {}
+        self._siblings = None
+        self._siblings_dev = {}
         self._norms = {}
 
     @property
@@ -228,6 +230,34 @@ class Taxonomy:
             mk = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
             self._parents_dev[key] = (mk(self.parent_tables()[1]), mk(self.leaf_paths.astype(np.int32)))
         return self._parents_dev[key]
+
+    def sibling_tables(self):
+        """(sib_ptr [G + 1], sib_col [N]) as numpy int32, built once: the sibling groups of the
+        conditional softmax (hvk_cond_softmax_*) as a CSR over the concatenated column space [0, N)
+        of parent_tables().  G = 1 + tier_off[6] groups, the root's first, then by (parent tier,
+        parent id): group 0 holds the tier-0 columns, group 1 + tier_off[t - 1] + p the columns of
+        the children of node p of tier t - 1, ascending, so tier t's columns are CSR positions
+        [tier_off[t], tier_off[t + 1]).  `identity_siblings`: sib_col is arange(N) (iNat21-style
+        names, Taxonomy.synthetic), and the kernels are handed no sib_col at all."""
+        if self._siblings is None:
+            off, parents = self.parent_tables()
+            group = np.zeros(off[-1], np.int64)  # a column's group, from its parent
+            for t in range(1, N_TIERS):
+                group[off[t]:off[t + 1]] = 1 + off[t - 1] + parents[off[t] - off[1]:off[t + 1] - off[1]]
+            sib_col = np.argsort(group, kind="stable").astype(np.int32)
+            sib_ptr = np.r_[0, np.cumsum(np.bincount(group, minlength=1 + off[N_TIERS - 1]))].astype(np.int32)
+            self.identity_siblings = bool(np.all(sib_col == np.arange(off[-1])))
+            self._siblings = (sib_ptr, sib_col)
+        return self._siblings
+
+    def device_sibling_tables(self, device):
+        """(sib_ptr, sib_col or None where it is the identity) of sibling_tables() on `device`."""
+        key = str(device)
+        if key not in self._siblings_dev:
+            sib_ptr, sib_col = self.sibling_tables()
+            mk = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+            self._siblings_dev[key] = (mk(sib_ptr), None if self.identity_siblings else mk(sib_col))
+        return self._siblings_dev[key]
 
     def soft_tables(self):
         """The node-slot tables of the soft-target HXE kernels (numpy int32, built once).
@@ -483,6 +513,47 @@ class SoftLabelsCrossEntropy(torch.nn.Module):
                                              self.level_weight)
 
 
+class ConditionalSoftmaxCrossEntropy(torch.nn.Module):
+    """The conditional (hierarchical) softmax over the MultitaskHead's node logits (Redmon &
+    Farhadi, CVPR 2017; Valmadre, NeurIPS 2022): the softmax of a node runs over its siblings only,
+    a leaf's probability is the product of the conditionals along its path, and the loss is
+    sum_t coeffs[t] * -log p(y_t | y_{t-1}) (ops.cond_softmax_cross_entropy, hvk_cond_softmax_fwd /
+    _bwd), the batch mean.  The reference has no such loss: parity unpinned, pinned by a float64
+    restatement and closed-form tests.
+
+    forward(outputs: the list of 7 tier logits, targets [B, 7] tier ids or [B] leaf ids).
+    `coeffs`: 7 tier coefficients, None or empty = 1 each; `smoothing`: label smoothing WITHIN the
+    target's sibling group, in [0, 1).  Per-tier probability targets (LabelSmoothing's list) are
+    refused: smoothing every tier on its own is no distribution over paths."""
+
+    def __init__(self, taxonomy: Taxonomy, coeffs=None, smoothing=0.0):
+        super().__init__()
+        self.taxonomy = taxonomy
+        self.coeffs = tuple(float(c) for c in coeffs) if coeffs is not None and len(coeffs) else (1.0,) * N_TIERS
+        self.smoothing = float(smoothing)
+        if len(self.coeffs) != N_TIERS:
+            raise ValueError(f"coeffs: {N_TIERS} tier coefficients, got {len(self.coeffs)}")
+        if not 0.0 <= self.smoothing < 1.0:
+            raise ValueError(f"smoothing ({smoothing}) outside [0, 1)")
+        self.tier_nll = None  # the last batch's per-tier terms, f32 [B, 7]
+
+    def forward(self, outputs, targets):
+        if isinstance(targets, (list, tuple)) or targets.dtype.is_floating_point:
+            raise ValueError("the conditional-softmax loss takes integer targets ([B, 7] tier ids or [B] leaf "
+                             "ids), not probability targets: smooth within the sibling groups with smoothing=")
+        if not isinstance(outputs, (list, tuple)) or [o.shape[1] for o in outputs] != list(self.taxonomy.num_classes):
+            raise ValueError(f"the conditional softmax takes the {N_TIERS} tier logits of the taxonomy "
+                             f"{list(self.taxonomy.num_classes)}")
+        dev = outputs[-1].device
+        parents, paths = self.taxonomy.device_parent_tables(dev)
+        if targets.ndim == 1:
+            targets = paths[targets.long()]
+        loss, self.tier_nll, _ = ops.cond_softmax_cross_entropy(
+            outputs, targets, parents, *self.taxonomy.device_sibling_tables(dev), coeffs=self.coeffs,
+            smoothing=self.smoothing, return_tiers=True)
+        return loss
+
+
 # --------------------------------------------------------------------------- metrics
 def fine_grained_predictions(output, topk=1, hierarchy_level=-1):
     """Top-k predictions of the finest tier (hierarchy.py:371-388)."""
@@ -528,6 +599,36 @@ def joint_predictions(outputs, taxonomy, weights=None):
     """argmax_k of joint_scores, int64 [B] (the lowest k among equal scores), without storing the
     scores."""
     return _joint_decode(outputs, taxonomy, weights, False)["pred"].long()
+
+
+def _cond_decode(outputs, targets, taxonomy, state, topk=5, want_scores=False, scores_out=None):
+    if not isinstance(outputs, (list, tuple)) or len(outputs) != N_TIERS:
+        raise ValueError(f"conditional-softmax decoding takes the list of {N_TIERS} tier logits")
+    if [o.shape[1] for o in outputs] != list(taxonomy.num_classes):
+        raise ValueError(f"tier logits {[o.shape[1] for o in outputs]} do not fit the taxonomy "
+                         f"{list(taxonomy.num_classes)}")
+    dev = outputs[-1].device
+    parents, paths = taxonomy.device_parent_tables(dev)
+    if targets is None:
+        targets = torch.zeros(outputs[-1].shape[0], device=dev, dtype=torch.int64)
+    if state is None:
+        state = torch.zeros(EvalMetrics.N_STATE, device=dev, dtype=torch.float64)
+    return ops.cond_softmax_decode(outputs, targets, parents, *taxonomy.device_sibling_tables(dev), paths, state,
+                                   topk=topk, want_scores=want_scores, scores_out=scores_out)
+
+
+def cond_softmax_scores(outputs, taxonomy):
+    """The leaf log-probabilities f32 [B, L] of the conditional softmax over the 7 tier logits
+    (ops.cond_softmax_decode, hvk_cond_softmax_decode): log p(k) = sum_t log p(anc_t(k) | anc_{t-1}(k)),
+    normalised by construction.  They are [B, L] scores like any leaf logits: crm_predictions,
+    backoff_predictions and BackoffMetrics take them as they are."""
+    return _cond_decode(outputs, None, taxonomy, None, want_scores=True)["scores"]
+
+
+def cond_softmax_predictions(outputs, taxonomy):
+    """argmax_k of cond_softmax_scores, int64 [B] (the lowest k among equal scores), without
+    storing the scores."""
+    return _cond_decode(outputs, None, taxonomy, None)["pred"].long()
 
 
 def _backoff_decode(outputs, targets, taxonomy, thresholds, state):
@@ -744,6 +845,13 @@ class EvalMetrics(torch.nn.Module):
     "joint-crm" also runs CRM on the joint scores: "acc@1/joint-crm", "tree-dist/joint-crm".  Both
     need a `taxonomy` and list outputs of 7 tiers.
 
+    decoding="cond" is for conditional-softmax checkpoints (ConditionalSoftmaxCrossEntropy): the 7
+    tier outputs are node logits, decoded into the leaf distribution log p(k) = sum_t log p(anc_t(k)
+    | anc_{t-1}(k)) (ops.cond_softmax_decode), and the standard keys -- "acc@1", "acc@{topk}",
+    "cross-entropy", "tree-dist", "acc@1/tier0".."tier6" -- are THAT distribution's, in `state`; the
+    species logits alone mean nothing there.  "cond-crm" also runs CRM on the decoded scores:
+    "acc@1/crm", "tree-dist/crm".  Both need a `taxonomy` and list outputs of 7 tiers.
+
     The running sums are `state`, 16 doubles on the device (layout: include/hvk.h); it is the
     module's only state_dict entry (with `joint_state` for the joint decodings).  update() launches and returns without a host
     synchronisation, so it can be captured in a HIP graph (move the module to the device first);
@@ -751,7 +859,7 @@ class EvalMetrics(torch.nn.Module):
 
     N_STATE = 16
 
-    DECODINGS = ("argmax", "crm", "joint", "joint-crm")
+    DECODINGS = ("argmax", "crm", "joint", "joint-crm", "cond", "cond-crm")
 
     def __init__(self, tree_dists=None, taxonomy=None, topk=5, decoding="argmax", tier_weights=None):
         super().__init__()
@@ -762,7 +870,8 @@ class EvalMetrics(torch.nn.Module):
         if decoding == "crm" and tree_dists is None and taxonomy is None:
             raise ValueError("decoding='crm' needs tree_dists or a taxonomy")
         self.joint = decoding in ("joint", "joint-crm")
-        if self.joint and taxonomy is None:
+        self.cond = decoding in ("cond", "cond-crm")
+        if (self.joint or self.cond) and taxonomy is None:
             raise ValueError(f"decoding={decoding!r} needs a taxonomy")
         if tier_weights is not None and (not self.joint or len(tier_weights) != N_TIERS):
             raise ValueError(f"tier_weights: {N_TIERS} weights, with a joint decoding only")
@@ -805,7 +914,7 @@ class EvalMetrics(torch.nn.Module):
     @torch.no_grad()
     def update(self, outputs, targets):
         tiers = outputs
-        if self.joint and (not isinstance(outputs, (list, tuple)) or len(outputs) != N_TIERS):
+        if (self.joint or self.cond) and (not isinstance(outputs, (list, tuple)) or len(outputs) != N_TIERS):
             raise ValueError(f"decoding={self.decoding!r} takes the list of {N_TIERS} tier logits")
         if isinstance(outputs, (list, tuple)):
             outputs = outputs[-1]  # the finest tier's logits, as FineGrainedAccuracy scores
@@ -813,6 +922,18 @@ class EvalMetrics(torch.nn.Module):
             raise ValueError("EvalMetrics takes integer class targets")
         if self.state.device != outputs.device:
             self.to(outputs.device)
+        if self.cond:
+            crm = self.decoding == "cond-crm"
+            B, L = outputs.shape
+            ws = ops._workspace("cond_softmax", outputs.device, 4 * B * L).view(B, L) if crm else None
+            out = _cond_decode(tiers, targets, self.taxonomy, self.state, topk=self.topk, want_scores=crm,
+                               scores_out=ws)
+            self.pred, self.rank, self.nll, self.dist, self.tier_hit = (out[k] for k in
+                                                                        ("pred", "rank", "nll", "dist", "tier_hit"))
+            if crm:
+                self.crm_pred, self.crm_risk, self.crm_dist = ops.crm_predict(out["scores"], targets,
+                                                                              self._crm_matrix(), self.state)
+            return
         kw = {}
         if self.leaf_paths is not None:  # path mode (also when a matrix was given as well)
             if targets.ndim == 2 and targets.shape[1] == N_TIERS:
@@ -865,7 +986,7 @@ class EvalMetrics(torch.nn.Module):
         if self.leaf_paths is not None:
             for t in range(N_TIERS):
                 out[f"acc@1/tier{t}"] = div(s[6 + t])
-        if self.decoding == "crm":
+        if self.decoding in ("crm", "cond-crm"):
             out["acc@1/crm"] = div(s[13])
             out["tree-dist/crm"] = div(s[14])
         if self.joint:

@@ -4,9 +4,10 @@
 SwinV2 registry (the reference calls timm.create_model, models.py:19/25, which
 is absent offline; the registry gives the official SwinV2 geometries with the
 semantics of swinv2.py).  ``build_composer_model`` picks the loss by
-``config.hierarchy.variant`` in {"", "multitask", "hxe", "soft-labels"} (models.py:105-114;
-"hxe" is implemented here, the reference raises; "soft-labels" is the soft-labels loss of the
-same paper, which the reference does not have).  ``Model`` keeps the
+``config.hierarchy.variant`` in {"", "multitask", "hxe", "soft-labels", "cond-softmax"}
+(models.py:105-114; "hxe" is implemented here, the reference raises; "soft-labels" is the
+soft-labels loss of the same paper and "cond-softmax" the conditional softmax over the multitask
+head's node logits, neither of which the reference has).  ``Model`` keeps the
 ComposerModel method surface: forward(batch), loss(outputs, batch),
 get_metrics(is_train), update_metric(batch, outputs, metric).
 """
@@ -72,7 +73,7 @@ def build_model(config, num_classes, **model_kwargs):
     if isinstance(num_classes, int):
         model = create_model(config.model.name, num_classes=num_classes, **model_kwargs)
     elif isinstance(num_classes, tuple):
-        assert config.hierarchy.variant == "multitask", \
+        assert config.hierarchy.variant in ("multitask", "cond-softmax"), \
             "config.hierarchy.variant must be multitask to use with multiple tiers of classes!"
         model = create_model(config.model.name, num_classes=2, **model_kwargs)
         if hasattr(model, "fc"):
@@ -114,7 +115,7 @@ class Model(torch.nn.Module):
         # fused_metrics() needs to score what the dicts above score
         self._metrics_info = metrics_info
 
-    def fused_metrics(self, is_train=False, decoding="argmax"):
+    def fused_metrics(self, is_train=False, decoding=None):
         """A fresh hierarchy.EvalMetrics, on the parameters' device, reporting what
         get_metrics(is_train) reports (models.py:61-101) from one kernel pass per batch:
         acc@1, acc@5, cross-entropy, with tree-dist where the reference adds it (the validation
@@ -123,8 +124,12 @@ class Model(torch.nn.Module):
         the CRM prediction's acc@1 and tree-dist (EvalMetrics); it is handed the DatasetInfo's
         matrix, or else its taxonomy, also where the reference's set has no tree-dist.
         decoding="joint" / "joint-crm" (the "multitask" variant's list outputs) is handed the
-        DatasetInfo's taxonomy and adds the joint decoding's keys."""
+        DatasetInfo's taxonomy and adds the joint decoding's keys.  The "cond-softmax" variant's
+        outputs are node logits: its default is decoding="cond" ("cond-crm" adds CRM's keys), the
+        same keys from the decoded leaf distribution; every other variant's default is "argmax"."""
         variant, cfg_train, info = self._metrics_info or ("", True, None)
+        if decoding is None:
+            decoding = "cond" if variant == "cond-softmax" else "argmax"
         with_dist = (variant == "multitask" and not is_train) or not cfg_train
         tree_dists = info.tree_dists if info is not None and with_dist else None
         taxonomy = info.taxonomy if info is not None and variant in ("hxe", "soft-labels") else None
@@ -132,6 +137,8 @@ class Model(torch.nn.Module):
             tree_dists, taxonomy = (info.tree_dists, None) if info.tree_dists is not None else (None, info.taxonomy)
         if decoding in ("joint", "joint-crm") and info is not None and variant == "multitask":
             taxonomy = info.taxonomy
+        if decoding in ("cond", "cond-crm") and info is not None and variant == "cond-softmax":
+            tree_dists, taxonomy = None, info.taxonomy
         m = hierarchy.EvalMetrics(tree_dists=tree_dists, taxonomy=taxonomy, topk=5, decoding=decoding)
         p = next(self.parameters(), None)
         return m.to(p.device) if p is not None else m
@@ -158,6 +165,11 @@ class Model(torch.nn.Module):
 
     def update_metric(self, batch, outputs, metric):
         _, targets = batch
+        if (self._metrics_info or ("",))[0] == "cond-softmax" and isinstance(outputs, (list, tuple)) \
+                and not isinstance(metric, hierarchy.EvalMetrics):
+            # the other metric classes score leaf logits: the decoded leaf log-probabilities
+            outputs = hierarchy.cond_softmax_scores(outputs, self._metrics_info[2].taxonomy)
+            targets = targets[:, -1] if targets.ndim == 2 else targets
         metric.update(outputs, targets)
 
     def forward(self, batch):
@@ -169,12 +181,14 @@ def build_composer_model(config, dataset_info: DatasetInfo, **model_kwargs):
     """models.py:54-118 with the "hxe" branch implemented and a "soft-labels" one added."""
     variant = config.hierarchy.variant
     num_classes = dataset_info.num_classes
-    if variant in ("hxe", "soft-labels"):
+    if variant in ("hxe", "soft-labels", "cond-softmax"):
         tax = dataset_info.taxonomy
         if tax is None:
             raise ValueError(f"hierarchy.variant={variant} needs DatasetInfo.taxonomy")
-        num_classes = tax.num_leaves
+        num_classes = tuple(tax.num_classes) if variant == "cond-softmax" else tax.num_leaves
     model = build_model(config, num_classes, **model_kwargs)
+    if variant == "cond-softmax":  # the MultitaskHead model; the metrics below see decoded leaf scores
+        num_classes = tax.num_leaves
 
     # metrics (models.py:61-101): the same dict keys per variant; "hxe" and "soft-labels" score
     # their leaf logits as the flat variant does
@@ -209,6 +223,10 @@ def build_composer_model(config, dataset_info: DatasetInfo, **model_kwargs):
     elif variant == "soft-labels":
         loss_fn = hierarchy.SoftLabelsCrossEntropy(dataset_info.taxonomy,
                                                    beta=config.hierarchy.soft_labels_beta)
+    elif variant == "cond-softmax":
+        loss_fn = hierarchy.ConditionalSoftmaxCrossEntropy(dataset_info.taxonomy,
+                                                           coeffs=config.hierarchy.multitask_coeffs,
+                                                           smoothing=config.hierarchy.cond_softmax_smoothing)
     elif variant == "multitask":
         loss_fn = hierarchy.MultitaskCrossEntropy(coeffs=config.hierarchy.multitask_coeffs)
     elif variant == "":

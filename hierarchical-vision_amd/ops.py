@@ -2011,6 +2011,137 @@ def joint_decode(outputs, targets, parents, leaf_paths, weights, state, topk=5, 
     return out
 
 
+# --------------------------------------------------------------------------- conditional softmax
+def _cond_rows(outputs, parents, sib_ptr, sib_col):
+    """The 7 tiers' node logits as hvk_cond_softmax_* read them -- (buf, B, ld, c_off): one row
+    buffer (_joint_rows: the head GEMM's column views in place) -- with the tables checked against
+    the tier sizes (Taxonomy.device_parent_tables / device_sibling_tables)."""
+    buf, off = _joint_rows(outputs)
+    buf, B, _, ld = _row_view(buf, "outputs", (torch.float32, torch.bfloat16), cast=True)
+    for t, name, n in ((parents, "parents", off[7] - off[1]), (sib_ptr, "sib_ptr", off[6] + 2),
+                       (sib_col, "sib_col", off[7])):
+        if t is None and name == "sib_col":
+            continue  # the identity
+        if t.dtype != torch.int32 or t.ndim != 1 or t.numel() != n or t.device != buf.device or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 [{n}] on the logits' device, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    return buf, B, ld, off
+
+
+def _cond_coeffs(coeffs, smoothing):
+    c = [1.0] * 7 if coeffs is None or len(coeffs) == 0 else [float(x) for x in coeffs]
+    if len(c) != 7 or not all(0.0 <= x < float("inf") for x in c):
+        raise ValueError(f"coeffs must be 7 finite non-negative numbers, got {c}")
+    if not 0.0 <= float(smoothing) < 1.0:
+        raise ValueError(f"smoothing ({smoothing}) outside [0, 1)")
+    return (ctypes.c_float * 7)(*c), float(smoothing)
+
+
+class CondSoftmaxCE(torch.autograd.Function):
+    """The conditional-softmax loss over the 7 tiers' node logits; see include/hvk.h.  `tables` =
+    (targets int64 [B, 7], parents, sib_ptr, sib_col or None, coeffs, smoothing).  Returns the mean
+    loss and, not differentiable, the per-tier NLL and the group LSEs, [B, 7] each."""
+
+    @staticmethod
+    def forward(ctx, tables, *outputs):
+        targets, parents, sib_ptr, sib_col, coeffs, smoothing = tables
+        buf, B, ld, off = _cond_rows(outputs, parents, sib_ptr, sib_col)
+        c_coeffs, smoothing = _cond_coeffs(coeffs, smoothing)
+        dev = buf.device
+        row_loss = torch.empty(B, device=dev, dtype=torch.float32)
+        lse = torch.empty((B, 7), device=dev, dtype=torch.float32)
+        tier_nll = torch.empty((B, 7), device=dev, dtype=torch.float32)
+        ctx.args = (1 if buf.dtype == torch.bfloat16 else 0, B, ld, (ctypes.c_int * 8)(*off))
+        ctx.tail = (ptr(parents), ptr(sib_ptr), ptr(sib_col), c_coeffs, smoothing)
+        if B > 0:
+            call("hvk_cond_softmax_fwd", _dev_ptr(buf, "outputs"), *ctx.args, ptr(targets), *ctx.tail,
+                 ptr(row_loss), ptr(lse), ptr(tier_nll), stream())
+        ctx.save_for_backward(buf, targets, parents, sib_ptr, lse, *((sib_col,) if sib_col is not None else ()))
+        ctx.off, ctx.dtypes = off, [o.dtype for o in outputs]
+        ctx.mark_non_differentiable(tier_nll, lse)
+        return row_loss.mean(), tier_nll, lse
+
+    @staticmethod
+    def backward(ctx, gout, _gnll, _glse):
+        buf, targets, _, _, lse = ctx.saved_tensors[:5]
+        dtype, B, ld, c_off = ctx.args
+        off, n = ctx.off, 8 if dtype else 4
+        ldg = -(-off[7] // n) * n  # whole 16-B vectors: the one gradient buffer, pad columns zero
+        dlogits = torch.empty((B, ldg), device=buf.device, dtype=buf.dtype)
+        if B > 0:
+            call("hvk_cond_softmax_bwd", _dev_ptr(buf, "outputs"), dtype, B, ld, c_off, ptr(targets), *ctx.tail,
+                 ptr(lse), ptr(_f32(gout.reshape(1))), ptr(dlogits), ldg, stream())
+        views = [dlogits[:, a:b] for a, b in zip(off, off[1:])]  # each tier a column view of it
+        return (None, *(v if v.dtype == dt else v.to(dt) for v, dt in zip(views, ctx.dtypes)))
+
+
+def cond_softmax_cross_entropy(outputs, targets, parents, sib_ptr, sib_col=None, coeffs=None, smoothing=0.0,
+                               return_tiers=False):
+    """hvk_cond_softmax_fwd / _bwd (include/hvk.h): the conditional-softmax loss, the batch mean of
+    sum_t coeffs[t] * [LSE over y_t's siblings - (1 - smoothing) z_t[y_t] - smoothing * their mean].
+    `outputs`: the 7 tier logits [B, n_t] (f32 or bf16; the head GEMM's column views are read in
+    place); `targets`: integer [B, 7] tier ids; `parents`, `sib_ptr`, `sib_col` (None: identity) from
+    Taxonomy.device_parent_tables / device_sibling_tables; `coeffs` None or empty = 1 per tier.
+    The backward hands every tier a column view of one gradient buffer.  return_tiers: also the
+    per-tier terms and the group LSEs of the target's path, f32 [B, 7] each."""
+    if not isinstance(outputs, (list, tuple)) or len(outputs) != 7:
+        raise ValueError("the conditional softmax takes the list of 7 tier logits")
+    if targets.dtype.is_floating_point or targets.ndim != 2 or tuple(targets.shape) != (outputs[0].shape[0], 7):
+        raise ValueError(f"targets {tuple(targets.shape)} {targets.dtype} are not [B, 7] tier ids")
+    tables = (targets.to(torch.int64).contiguous(), parents, sib_ptr, sib_col, coeffs, smoothing)
+    loss, tiers, lse = CondSoftmaxCE.apply(tables, *outputs)
+    return (loss, tiers, lse) if return_tiers else loss
+
+
+def cond_softmax_supported(tier_sizes):
+    """hvk_cond_softmax_supported: whether hvk_cond_softmax_decode takes a taxonomy of these 7 tier
+    sizes (its tiers 0-5 stay in one workgroup's LDS; the loss has no such limit)."""
+    off = [0]
+    for n in tier_sizes:
+        off.append(off[-1] + int(n))
+    return len(off) == 8 and bool(_lib.load().hvk_cond_softmax_supported((ctypes.c_int * 8)(*off)))
+
+
+def cond_softmax_decode(outputs, targets, parents, sib_ptr, sib_col, leaf_paths, state, topk=5, want_scores=False,
+                        scores_out=None):
+    """hvk_cond_softmax_decode (include/hvk.h): the leaf distribution of the conditional softmax,
+    log p(k) = sum_t (z_t[anc_t(k)] - LSE over anc_t(k)'s siblings), from one read of the node
+    logits.  `outputs`, `targets` (leaf ids), `state` and `topk` as joint_decode takes them (the
+    state's slots 0-12 are added to); the tables as cond_softmax_cross_entropy's, `leaf_paths`
+    int32 [L, 7].  `want_scores`: also the f32 [B, L] log-probabilities (into `scores_out` when
+    given).  Not differentiable, no host synchronisation.  Returns a dict of per-row tensors: pred,
+    rank, nll, lse, dist, tier_hit, scores."""
+    buf, B, ld, off = _cond_rows(outputs, parents, sib_ptr, sib_col)
+    buf, B, _, ld, targets, t_stride, t_off = _eval_rows(buf, targets, "cond_softmax_decode")
+    dev, L = buf.device, off[7] - off[6]
+    if state.dtype != torch.float64 or state.numel() != 16 or not state.is_contiguous():
+        raise ValueError("state must be a contiguous float64 tensor of 16 elements")
+    if leaf_paths.dtype != torch.int32 or tuple(leaf_paths.shape) != (L, 7):
+        raise ValueError(f"leaf_paths must be int32 [{L}, 7]")
+    if topk < 1:
+        raise ValueError(f"topk ({topk}) < 1")
+    c_off = (ctypes.c_int * 8)(*off)
+    if not _lib.load().hvk_cond_softmax_supported(c_off):
+        raise RuntimeError(f"hvk_cond_softmax_decode does not take tier sizes {[b - a for a, b in zip(off, off[1:])]}: "
+                           "tiers 0-5 must fit one workgroup's LDS (15360 nodes)")
+    mk = lambda *shape, dtype=torch.int32: torch.empty(*shape, device=dev, dtype=dtype)  # noqa: E731
+    out = dict(pred=mk(B), rank=mk(B), nll=mk(B, dtype=torch.float32), lse=mk(B, dtype=torch.float32), dist=mk(B),
+               tier_hit=mk(B, dtype=torch.uint8), scores=None)
+    if want_scores:
+        if scores_out is None:
+            scores_out = mk(B, L, dtype=torch.float32)
+        elif scores_out.dtype != torch.float32 or tuple(scores_out.shape) != (B, L) or not scores_out.is_contiguous():
+            raise ValueError(f"scores_out must be a contiguous float32 [{B}, {L}]")
+        out["scores"] = scores_out
+    if B == 0:
+        return out
+    call("hvk_cond_softmax_decode", _dev_ptr(buf, "outputs"), 1 if buf.dtype == torch.bfloat16 else 0, B, ld, c_off,
+         _dev_ptr(targets, "targets"), t_stride, t_off, ptr(parents), ptr(sib_ptr), ptr(sib_col), ptr(leaf_paths),
+         int(topk), ptr(out["pred"]), ptr(out["rank"]), ptr(out["nll"]), ptr(out["lse"]), ptr(out["dist"]),
+         ptr(out["tier_hit"]), ptr(out["scores"]), ptr(state), stream())
+    return out
+
+
 # --------------------------------------------------------------------------- back-off decoding
 BACKOFF_MAX_THRESHOLDS = 32
 

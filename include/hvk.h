@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 24
+#define HVK_ABI_VERSION 25
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -876,6 +876,64 @@ int hvk_backoff_decode(const void* logits, int logits_dtype /* 0 f32, 1 bf16 */,
                        const int* child_lo, const int* child_hi, const int* slot_node, const int* leaf_paths,
                        const float* thresholds, int n_thresholds, int* path, float* prob, int* match,
                        double* state, void* stream);
+
+/* ---- Conditional-softmax taxonomy head: loss, gradient and leaf decoding ------------------------
+ * Every node of the taxonomy has a logit, laid out as hvk_joint_decode's (all tiers side by side,
+ * tier t = columns [tier_off[t], tier_off[t + 1]), f32 or bf16, any row stride ld >= tier_off[7],
+ * read in place).  The softmax runs over a node's SIBLINGS only -- the group g(n) of a tier-t node
+ * n is the children of its tier-(t - 1) parent, the tier-0 nodes are one group under the root:
+ *   log p(n | parent) = z_t[n] - LSE_{m in g(n)} z_t[m]
+ *   log p(leaf k)     = sum_{t = 0..6} log p(anc_t(k) | anc_(t-1)(k))        (sum_k p(k) = 1)
+ *   loss(y)           = sum_t lam_t [ LSE_{g(y_t)} - (1 - eps) z_t[y_t] - eps mean_{m in g(y_t)} z_t[m] ]
+ * with 7 tier coefficients lam (HOST float [7], finite, >= 0) and eps in [0, 1) label smoothing
+ * within the sibling group.  The gradient of the batch-mean loss is
+ *   lam_t / B (softmax_g(m) - (1 - eps) [m = y_t] - eps / |g|)
+ * on the 7 groups of the target's path and exactly zero on every other column; an only child has
+ * log p = 0, loss term 0 and gradient 0 exactly.
+ * Tables (device int; hierarchy.Taxonomy.sibling_tables / parent_tables): parents as
+ * hvk_joint_decode's; sib_ptr [G + 1], sib_col [tier_off[7]] a CSR of the groups over the column
+ * space, G = 1 + tier_off[6]: group 0 the root's children, group 1 + tier_off[t - 1] + p the children
+ * of node p of tier t - 1, so tier t's columns are CSR positions [tier_off[t], tier_off[t + 1]).
+ * sib_col NULL: the identity (column j at position j).  Every table entry is clamped into the range
+ * it indexes before it is followed.
+ *
+ * hvk_cond_softmax_fwd: targets int64 [B, 7] tier ids (contiguous).  One wave per row reads only
+ * the 7 groups of the target's path.  row_loss f32 [B]; lse f32 [B, 7] the group LSEs (saved for
+ * the backward); tier_nll f32 [B, 7] the bracketed per-tier terms, without lam.  A row whose target
+ * is not a path of the taxonomy -- an id outside its tier, or parent(y_t) != y_(t-1) -- gets NaN in
+ * all three, as hvk_hxe_fwd treats an out-of-range id, and reads nothing out of range.
+ * hvk_cond_softmax_bwd: dlogits [B, ldg] in the logits' dtype, ldg >= tier_off[7] a whole number
+ * of 16-B vectors, 16-B aligned; EVERY element is written, pad columns (>= tier_off[7]) with zeros,
+ * in one sweep of 16-B stores; a vector outside the row's 7 groups stores zeros without reading a
+ * logit.  gout: device f32 [1], the gradient of the mean loss.  A row that is not a path gets NaN
+ * in its tier_off[7] columns.  B <= 65535.
+ * hvk_cond_softmax_decode: per row, scores[b, k] = log p(k) (f32 [B, L] dense or NULL: not stored),
+ * lse[b] = log sum_k exp(scores) (0 up to rounding), and pred, rank, nll = lse - score of the target,
+ * dist, tier_hit exactly as hvk_joint_decode defines them on its scores (targets, t_stride, t_off:
+ * leaf ids as hvk_eval_metrics; an invalid target: rank -1, nll NaN, dist -1, tier_hit 0); state: a
+ * double [16], slots [0..12] added to, the others untouched.  One workgroup per row stages tiers
+ * 0-5 in LDS as f32 and walks top-down, one barrier a tier, a work item being a parent: a group of
+ * at most 32 children is reduced by one lane, a wider one by a whole wave; the path depends on the
+ * group's size alone.  Limit: tiers 0-5 hold at most 15360 nodes, as hvk_joint_decode; above it
+ * HVK_EUNSUPPORTED, and hvk_cond_softmax_supported(tier_off) returns 0 (also for malformed
+ * offsets).  L <= 2^24.  The loss has no such limit.
+ * All three: fixed summation orders, no atomics (equal inputs give bit-identical outputs), NaN
+ * logits never fault, no synchronisation or allocation (capturable).  One launch each (decode:
+ * two).  B == 0 returns HVK_OK without a launch.  ABI 25. */
+int hvk_cond_softmax_supported(const int* tier_off);
+int hvk_cond_softmax_fwd(const void* logits, int logits_dtype /* 0 f32, 1 bf16 */, int B, int ld,
+                         const int* tier_off, const int64_t* targets, const int* parents, const int* sib_ptr,
+                         const int* sib_col, const float* coeffs, float smoothing, float* row_loss, float* lse,
+                         float* tier_nll, void* stream);
+int hvk_cond_softmax_bwd(const void* logits, int logits_dtype, int B, int ld, const int* tier_off,
+                         const int64_t* targets, const int* parents, const int* sib_ptr, const int* sib_col,
+                         const float* coeffs, float smoothing, const float* lse, const float* gout,
+                         void* dlogits, int ldg, void* stream);
+int hvk_cond_softmax_decode(const void* logits, int logits_dtype, int B, int ld, const int* tier_off,
+                            const int64_t* targets, int t_stride, int t_off, const int* parents,
+                            const int* sib_ptr, const int* sib_col, const int* leaf_paths, int topk, int* pred,
+                            int* rank, float* nll, float* lse, int* dist, unsigned char* tier_hit, float* scores,
+                            double* state, void* stream);
 
 #ifdef __cplusplus
 }
