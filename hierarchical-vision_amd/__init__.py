@@ -9,6 +9,7 @@ Modules mirror the reference files they replace:
   configs.py     <- configs.py     (structured config schema)
   simpleshot.py  <- simpleshot.py  (nearest-centroid evaluation of frozen features, flat / hierarchical)
   linear_probe.py <- linear_probe.py (StandardScaler + one-vs-rest logistic fit + grid search, on the device)
+  knn.py            weighted k-nearest-neighbour evaluation of frozen features (bf16 bank, fused top-k and tier vote)
   ddp.py            RCCL gradient all-reduce, bucketed, overlapped with backward
   ops.py            autograd Functions over the C ABI of libhvk.so
   _lib.py           ctypes binding of libhvk.so (include/hvk.h)

@@ -151,10 +151,14 @@ SIGNATURES = {
     "hvk_cond_softmax_bwd": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _i, _p]),
     "hvk_cond_softmax_decode": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p,
                                      _p, _p]),
+    "hvk_knn_supported": (_i, [_i, _i]),
+    "hvk_knn_workspace": (_sz, [_i, _i, _i, _i]),
+    "hvk_knn_topk": (_i, [_p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "hvk_knn_vote": (_i, [_p, _p, _i, _i, _p, _i, _i, _p, _i, _f, _p, _p, _p]),
 }
 
 _lib = None
-ABI_VERSION = 25  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
+ABI_VERSION = 26  # include/hvk.h's HVK_ABI_VERSION, the ABI this binding's SIGNATURES describe
 
 
 def load():

@@ -13,7 +13,7 @@ Args = dict  # str -> Any
 @dataclass
 class ModelConfig:
     name: str = "resnet50"
-    variant: str = "full-tuning"  # full-tuning | linear-probe | simpleshot[-l2n|-cl2n]
+    variant: str = "full-tuning"  # full-tuning | linear-probe | simpleshot[-l2n|-cl2n] | knn
     pretrained_checkpoint: Optional[str] = None
 
 
@@ -71,6 +71,16 @@ class SimpleShotConfig:
 
 
 @dataclass
+class KnnConfig:
+    """Weighted k-NN evaluation (hvamd.knn): the values of k reported (at most 8, each <= 256),
+    the temperature of the vote weights (Wu et al., CVPR 2018) and whether the features are
+    divided by their row mean before the L2 normalisation, as SimpleShotConfig.centered."""
+    k: list = field(default_factory=lambda: [10, 20, 100, 200])
+    temperature: float = 0.07
+    centered: bool = False
+
+
+@dataclass
 class AlgorithmConfig:
     cls: str = ""
     args: dict = field(default_factory=dict)
@@ -111,6 +121,7 @@ class Config:
     save: SaveConfig = field(default_factory=SaveConfig)
     wandb: WandbConfig = field(default_factory=WandbConfig)
     simpleshot: SimpleShotConfig = field(default_factory=SimpleShotConfig)
+    knn: KnnConfig = field(default_factory=KnnConfig)
 
 
 def _merge(obj, data, path="config"):

@@ -87,7 +87,7 @@ def build_model(config, num_classes, **model_kwargs):
     model.apply(weight_init)
     if config.model.variant == "full-tuning":
         pass
-    elif config.model.variant in ("linear-probe", "simpleshot", "simpleshot-l2n", "simpleshot-cl2n"):
+    elif config.model.variant in ("linear-probe", "simpleshot", "simpleshot-l2n", "simpleshot-cl2n", "knn"):
         model = FeatureOnlyModel(model)
     else:
         raise ValueError(config.model.variant)

@@ -2496,3 +2496,77 @@ def lp_step(W, b, Yw, Yb, dW, db, t, step, tol, gmax, converged, frozen=None):
         raise ValueError(f"step {step} must be > 0 and tol {tol} >= 0")
     call("hvk_lp_step", ptr(W), ptr(b), ptr(Yw), ptr(Yb), ptr(dW), ptr(db), ptr(t), ptr(frozen), R, D, float(step),
          float(tol), ptr(gmax), ptr(converged), stream())
+
+
+# --------------------------------------------------------------------------- k-nearest neighbours
+_KNN_WORKSPACE = {}  # device -> uint8 buffer of hvk_knn_topk's per-split lists
+
+
+def knn_supported(D, k):
+    """hvk_knn_supported: whether hvk_knn_topk serves feature width D and k neighbours."""
+    return bool(_lib.load().hvk_knn_supported(int(D), int(k)))
+
+
+def _knn_bf16(x, what):
+    if not x.is_cuda:
+        raise RuntimeError(f"libhvk ops run on the GPU only; got a CPU tensor ({what})")
+    if x.ndim != 2 or x.dtype != torch.bfloat16 or not x.is_contiguous():
+        raise ValueError(f"{what} must be contiguous bfloat16 [rows, D], got {x.dtype} {tuple(x.shape)}")
+    return x.detach()
+
+
+def knn_topk(q, bank, k, n=None, splits=0):
+    """hvk_knn_topk: the k largest q . b of every row of `q` (bf16 [B, D]) over the first `n`
+    rows (default: all) of `bank` (bf16 [>= n, D]), both L2-normalised already: (sims f32 [B, k],
+    idx int32 [B, k]) ordered by (similarity descending, bank index ascending); (-inf, -1) past
+    n.  `splits`: bank splits, 0 planned; the result does not depend on it."""
+    q, bank = _knn_bf16(q, "q"), _knn_bf16(bank, "bank")
+    B, D = q.shape
+    n = bank.shape[0] if n is None else int(n)
+    if bank.shape[1] != D or not 1 <= n <= bank.shape[0]:
+        raise ValueError(f"bank {tuple(bank.shape)} with n = {n} rows does not fit q {tuple(q.shape)}")
+    k, splits = int(k), int(splits)
+    if k < 1 or splits < 0:
+        raise ValueError(f"k {k} must be >= 1 and splits {splits} >= 0")
+    if not knn_supported(D, k):
+        raise RuntimeError(f"hvk_knn_topk does not serve D = {D}, k = {k} (D % 8 == 0, D <= 1024, k <= 256)")
+    sims = torch.empty(B, k, device=q.device, dtype=torch.float32)
+    idx = torch.empty(B, k, device=q.device, dtype=torch.int32)
+    if B == 0:
+        return sims, idx
+    need = _lib.load().hvk_knn_workspace(B, n, k, splits)
+    ws = _KNN_WORKSPACE.get(q.device)
+    if ws is None or ws.numel() < need:
+        ws = _KNN_WORKSPACE[q.device] = torch.empty(max(need, 1 << 20), device=q.device, dtype=torch.uint8)
+    call("hvk_knn_topk", ptr(q), B, ptr(bank), n, D, k, splits, ptr(sims), ptr(idx), ptr(ws), ws.numel(), stream())
+    return sims, idx
+
+
+def knn_vote(sims, idx, labels, ks, temperature=0.07):
+    """hvk_knn_vote: from knn_topk's (sims, idx) and the bank's tier ids `labels` (int32 [N] or
+    [N, T], T 1 or 7), for each k_j of `ks` (at most 8, each <= k): (leaf int32 [n_k, B], the leaf
+    of largest weighted vote; path int32 [n_k, B, T], the top-down walk)."""
+    if not (sims.is_cuda and idx.is_cuda and labels.is_cuda):
+        raise RuntimeError("libhvk ops run on the GPU only; got a CPU tensor (sims / idx / labels)")
+    if (sims.ndim != 2 or sims.dtype != torch.float32 or idx.dtype != torch.int32 or idx.shape != sims.shape
+            or not sims.is_contiguous() or not idx.is_contiguous()):
+        raise ValueError("sims must be contiguous float32 [B, k] and idx int32 [B, k]")
+    if labels.ndim == 1:
+        labels = labels[:, None]
+    if labels.ndim != 2 or labels.dtype != torch.int32 or labels.shape[1] not in (1, 7) or labels.shape[0] < 1:
+        raise ValueError(f"labels must be int32 [N] or [N, 1 | 7], got {labels.dtype} {tuple(labels.shape)}")
+    labels = labels if labels.is_contiguous() else labels.contiguous()
+    B, k = sims.shape
+    N, T = labels.shape
+    ks = [int(v) for v in ks]
+    if not 1 <= len(ks) <= 8 or min(ks) < 1 or max(ks) > k:
+        raise ValueError(f"ks {ks}: 1 to 8 values in [1, k = {k}]")
+    if not float(temperature) > 0.0:
+        raise ValueError(f"temperature {temperature} must be positive")
+    leaf = torch.empty(len(ks), B, device=sims.device, dtype=torch.int32)
+    path = torch.empty(len(ks), B, T, device=sims.device, dtype=torch.int32)
+    if B == 0:
+        return leaf, path
+    call("hvk_knn_vote", ptr(sims), ptr(idx), B, k, ptr(labels), N, T, (ctypes.c_int * len(ks))(*ks), len(ks),
+         float(temperature), ptr(leaf), ptr(path), stream())
+    return leaf, path

@@ -23,7 +23,7 @@ extern "C" {
 #endif
 
 /* the C ABI this header describes; hvk_abi_version() returns it (bindings check it at load) */
-#define HVK_ABI_VERSION 25
+#define HVK_ABI_VERSION 26
 
 #define HVK_OK 0
 #define HVK_EINVAL 1
@@ -934,6 +934,41 @@ int hvk_cond_softmax_decode(const void* logits, int logits_dtype, int B, int ld,
                             const int* sib_ptr, const int* sib_col, const int* leaf_paths, int topk, int* pred,
                             int* rank, float* nll, float* lse, int* dist, unsigned char* tier_hit, float* scores,
                             double* state, void* stream);
+
+/* ---- Weighted k-nearest-neighbour evaluation (Wu et al., CVPR 2018) ---------------------------
+ * The third protocol on frozen features beside the nearest centroid and the linear probe: the
+ * bank is the training set itself, bf16 [N, D] dense rows, already L2-normalised (hvk_ss_prepare,
+ * rounded to bf16 by the caller), the queries q bf16 [B, D] likewise.  Both 16-byte aligned.
+ * Supported: D % 8 == 0, D <= 1024, 1 <= k <= 256 (hvk_knn_supported(D, k) returns 1); anything
+ * else is HVK_EUNSUPPORTED.  1 <= N <= 2^31 - 256.
+ *
+ * hvk_knn_topk: per query row the k largest s = q . b as sims f32 [B, k] and their bank rows as
+ * idx int32 [B, k], ordered by (similarity descending, bank index ascending), which is also the
+ * tie rule; with N < k the tail is (-inf, -1).  A bf16 MFMA sweep (f32 accumulation of exact
+ * products) whose scores leave the accumulators only through a running top-k per row in LDS; a
+ * NaN score is never selected.  The bank is split over workgroups (`splits`, 0: planned from the
+ * shape); every split leaves its k best in `workspace` (hvk_knn_workspace(B, N, k, splits) bytes,
+ * 4-byte aligned) and a second kernel merges and orders them.  A score is one fixed chain of MFMAs
+ * whatever tile or split its bank row falls in: the output is bit-identical for any `splits`.
+ *
+ * hvk_knn_vote: from sims / idx as above (any idx outside [0, N) counts as a pad) and the bank's
+ * tier ids labels int32 [N, T], T 1 or 7 (a neighbour with a negative id takes no part), for each
+ * of the n_k <= 8 prefixes ks[j] <= k (a host array): weights w_i = exp((s_i - s_0) / temperature),
+ * a label's vote the sum of w over the neighbours that carry it, in ascending rank.
+ *   leaf int32 [n_k, B]    the leaf (column T - 1) of largest vote, the lower id among equal votes;
+ *   path int32 [n_k, B, T] top-down: tier 0 the node of largest vote, tier t + 1 the node of
+ *                          largest vote among the neighbours whose tier-t id is the node just
+ *                          chosen.  With labels that are paths of a tree it is a path of the tree.
+ * A row without a valid neighbour gets zeros.  One wave per row, pairwise label comparisons
+ * (k^2), no per-class array.
+ * Both: no atomics (equal inputs give bit-identical outputs), no synchronisation or allocation.
+ * B == 0 returns HVK_OK without a launch.  Two launches (topk), one (vote).  ABI 26. */
+int hvk_knn_supported(int D, int k);
+size_t hvk_knn_workspace(int B, int N, int k, int splits);
+int hvk_knn_topk(const void* q, int B, const void* bank, int N, int D, int k, int splits, float* sims, int* idx,
+                 void* workspace, size_t workspace_bytes, void* stream);
+int hvk_knn_vote(const float* sims, const int* idx, int B, int k, const int* labels, int N, int T, const int* ks,
+                 int n_k, float temperature, int* leaf, int* path, void* stream);
 
 #ifdef __cplusplus
 }
